@@ -15,9 +15,14 @@ For N > 1 there is one rank per GPU (the reference's MPI ranks, source/main.cpp:
 outer launcher (torch.distributed.run) has set RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*, or -- plain
 `python bench.py --gpus N` -- this process spawns the N ranks itself before it touches the GPU and relays
 rank 0's JSON line.  Chains never communicate during sweeps (source/main.cpp:128-171), so there is no
-data-path collective: scaling is weak, value = total sweeps / max time.  After the timed region the ranks
-run two replica-exchange rounds over the library's RCCL transport (dqmc_replica_exchange_round; cfg 4's
-wire) and report them under "replica_exchange" -- outside `value`.
+data-path collective: scaling is weak, value = total sweeps / max time.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, acceptance, wrap error).
+--dump-outputs DIR then writes what the last timed step left for a caller as DIR/<name>.npy (dump_outputs).
+--full adds everything else, after the timed region: the roofline of the local-update kernel from a HIP-event
+profiled pass of its own, the GEMM chain in situ, the batched chains, the CPU baseline with the parity leg, the
+cfg-5 block, and for N > 1 two replica-exchange rounds over the library's RCCL transport
+(dqmc_replica_exchange_round; cfg 4's wire) under "replica_exchange".  None of it enters `value`.
 """
 import argparse
 import json
@@ -32,6 +37,27 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (6.29 TB/s achievable)
 FP64_MFMA_PEAK_TFLOPS = 78.6  # 256 CU x 4 SIMD x 32 flop/clk x 2.4 GHz (AMD MI355X spec)
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, eng):
+    """What a caller of the timed path holds after its last step, one .npy per array, every array with a leading chain axis:
+    G.npy (float64, chain x N x N: the equal-time Green's function), fields.npy (float32, chain x Ltau x N: the HS fields, values
+    0..3), n_accepted.npy (float64: accepted proposals per chain since init) and chains.npy (float64: the chain index of each row).
+    When the chains together exceed DUMP_BUDGET_BYTES, a fixed, seeded sample of them is written."""
+    C, n, nt = eng.C, eng.n, eng.nt
+    G = np.asarray(eng.get_G(), dtype=np.float64).reshape(C, n, n)
+    fields = np.asarray(eng.get_fields(), dtype=np.float32).reshape(C, nt, n)
+    st = eng.stats()
+    acc = np.array([s.n_accepted for s in (st if isinstance(st, list) else [st])], dtype=np.float64)
+    keep = np.arange(C)
+    per_chain = G[0].nbytes + fields[0].nbytes + 2 * 8
+    budget = DUMP_BUDGET_BYTES - 4096                 # room for the four .npy headers
+    if C * per_chain > budget:
+        keep = np.sort(np.random.default_rng(0).choice(C, max(1, budget // per_chain), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("G", G[keep]), ("fields", fields[keep]), ("n_accepted", acc[keep]), ("chains", keep.astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def gen_streams(model, rng, C):
@@ -272,7 +298,14 @@ def main():
                          "different discretisation, reported with \"kinetic\": \"checkerboard\" and never comparable with the headline line")
     ap.add_argument("--no-cfg5", action="store_true", help="skip the BASELINE.json configs[4] block (24x24, Ltau = 400: init + 1 warm-up + 2 timed sweeps, ~5 s) of the N = 1 line")
     ap.add_argument("--no-replica-exchange", action="store_true", help="skip the RCCL replica-exchange rounds after the timed region (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline, the GEMM chain, the batched chains, the CPU baseline, the cfg-5 "
+                         "block and (N > 1) the replica exchange; --batched-*, --cpu-budget and the --no-* options only shape this part")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step left (G, HS fields, accepted counts; rank 0's chains) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -336,7 +369,6 @@ def main():
         sweep()
     eng.sync()
     st0 = eng.stats()
-    eng.set_profiling(True); eng.update_kernel_time()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -344,10 +376,10 @@ def main():
     eng.sync()
     barrier()
     dt = time.perf_counter() - t0
-    upd_ms, upd_launches, upd_acc = eng.update_kernel_time()
-    eng.set_profiling(False)
     st1 = eng.stats()
     dt = max_over_ranks(d, dt)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng)
 
     if rank == 0:
         n = model.n
@@ -355,13 +387,6 @@ def main():
         s0 = st0[0] if C > 1 or isinstance(st0, list) else st0
         s1 = st1[0] if C > 1 or isinstance(st1, list) else st1
         acc_rate = (s1.n_accepted - s0.n_accepted) / max(1, s1.n_proposed - s0.n_proposed)
-        # rank-1 update roofline: 16*N^2 algorithmic bytes per ACCEPTED proposal (read + write G once,
-        # SURVEY.md 8d); one launch = the local update of one time slice (all chains of this rank)
-        bytes_per_launch = 16.0 * n * n * upd_acc / max(1, upd_launches)
-        avg_launch_s = (upd_ms * 1e-3) / max(1, upd_launches)
-        achieved = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
-        # GEMM chain: G_alg = 6*Ltau + 8*n_stack - 10 dense GEMMs of 2N^3 flop per sweep (SURVEY.md 8d)
-        g_alg = 6 * model.nt + 8 * model.n_stack - 10
         out = {
             "metric": "MC sweeps/sec, 2D Hubbard N=256 Ltau=200", "value": total_sweeps / dt, "unit": "sweeps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
@@ -370,6 +395,27 @@ def main():
                        "chains_per_gpu": C, "n_chains_total": world * C, "parallelism": f"independent chains, {world} gpu x {C} chain"},
             "start": start, "kinetic": "checkerboard" if args.checkerboard else "dense exp(-dtau K) (the reference's)",
             "acceptance": acc_rate, "max_wrap_err": s1.max_err, "mean_wrap_err": s1.mean_err,
+        }
+    if args.full:
+        # the roofline's HIP events sit between the update launches, so they get a pass of their own after the timed region: as many
+        # sweeps as were timed, continuing the same chains (every rank runs it, to stay in step for the replica exchange)
+        eng.set_profiling(True); eng.update_kernel_time()
+        tp0 = time.perf_counter()
+        for _ in range(args.steps):
+            sweep()
+        eng.sync()
+        dt_prof = time.perf_counter() - tp0
+        upd_ms, upd_launches, upd_acc = eng.update_kernel_time()
+        eng.set_profiling(False)
+    if rank == 0 and args.full:
+        # rank-1 update roofline: 16*N^2 algorithmic bytes per ACCEPTED proposal (read + write G once,
+        # SURVEY.md 8d); one launch = the local update of one time slice (all chains of this rank)
+        bytes_per_launch = 16.0 * n * n * upd_acc / max(1, upd_launches)
+        avg_launch_s = (upd_ms * 1e-3) / max(1, upd_launches)
+        achieved = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
+        # GEMM chain: G_alg = 6*Ltau + 8*n_stack - 10 dense GEMMs of 2N^3 flop per sweep (SURVEY.md 8d)
+        g_alg = 6 * model.nt + 8 * model.n_stack - 10
+        out.update({
             "roofline": {"kernel": "local update of one time slice (" + ("slice_kernel: delayed-update walk + flush roles" if n <= 256 else
                                                                          "slice_sm_kernel: sub-matrix walk + flush roles") + ")", "bound": "hbm",
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
@@ -379,10 +425,10 @@ def main():
                          "traffic": pmc_traffic(args.config, C),
                          "algorithmic_bytes_per_launch": bytes_per_launch, "avg_launch_ms": avg_launch_s * 1e3,
                          "launches": upd_launches, "accepted": upd_acc,
-                         "time_share_of_sweep": (upd_ms * 1e-3) / dt},
+                         "time_share_of_sweep": (upd_ms * 1e-3) / dt_prof, "sweeps": args.steps},
             "gemm_chain": {"algorithmic_gemms_per_sweep": g_alg, "flop_per_sweep": g_alg * 2.0 * n ** 3,
                            "peak_tflops": FP64_MFMA_PEAK_TFLOPS},
-        }
+        })
         # GEMM chain in situ: 200 wraps (B G B^-1 then B^-1 G B: 4 GEMMs of 2N^3 flop, G returns to itself up to rounding) enqueued
         # back to back on the engine's stream, the way a sweep issues them; wall time / 800 = time per GEMM including its launch gap
         n_pairs = 200
@@ -424,12 +470,12 @@ def main():
             for (ee, _, _) in engs: ee.close()
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model, 12345, args.cpu_budget, lib, local_rank, args.config)
-        if args.rehearse_shared_gpu:
-            out["rehearsal"] = True                  # ranks share devices: the launch path is exercised, the number means nothing
+    if rank == 0 and args.rehearse_shared_gpu:
+        out["rehearsal"] = True                      # ranks share devices: the launch path is exercised, the number means nothing
     rex = None
-    if world > 1 and C == 1 and not args.no_replica_exchange and not args.rehearse_shared_gpu:
+    if args.full and world > 1 and C == 1 and not args.no_replica_exchange and not args.rehearse_shared_gpu:
         rex = replica_exchange_check(lib, eng, d)
-    if rank == 0 and world == 1 and C == 1 and args.config == "cfg3" and not args.checkerboard and not args.no_cfg5:
+    if args.full and rank == 0 and world == 1 and C == 1 and args.config == "cfg3" and not args.checkerboard and not args.no_cfg5:
         eng.close()                                   # hands back its CU reservation: the cfg-5 engine takes the persistent slice kernel as it does on its own
         out["cfg5"] = cfg5_block(lib, local_rank)
     if rank == 0:
