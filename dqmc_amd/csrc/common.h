@@ -36,6 +36,14 @@ const char* get_error();
         if (_rc != 0) return _rc;   \
     } while (0)
 
+// ---- device status block ----------------------------------------------------
+// 4 ints per context (Ctx::info, engine.hip), zeroed at creation, read and cleared by the host after a sync (take_status, engine.hip).
+//   word 0: OR of the bits below;  word 1: first abandoned time slice + 1 (DQ_STATUS_CENSUS);  words 2, 3: unused.
+constexpr int DQ_STATUS_PIVOT = 1;      // LU / Gauss-Jordan: zero or NaN pivot (lu_blocked.hip, lu_gj.hip)
+constexpr int DQ_STATUS_COOP_QR = 2;    // cooperative QRCP gave up waiting for a partner workgroup (qr_coop.hip)
+constexpr int DQ_STATUS_HANDOFF = 4;    // a hand-off of a persistent slice kernel timed out (update.hip, update_sm.hip)
+constexpr int DQ_STATUS_CENSUS = 8;     // the census of the sub-matrix slice kernel failed; word 1 holds the slice (update_sm.hip)
+
 // A batched column-major matrix: chain c lives at p + c*stride (stride 0 =
 // one matrix shared by all chains, e.g. expK when every chain has the same
 // beta).  Leading dimension is always n.
@@ -110,25 +118,26 @@ struct QrWork {
     int* jpvt; long jpvt_stride;       // n per chain
     unsigned long long* sync = nullptr; long sync_stride = 0;   // cooperative QRCP: granule records, >= qrcp_coop_sync_granules(n) per chain
     int* abort_words = nullptr;                                 // cooperative QRCP: one word per chain
-    int* info = nullptr;                                        // |= 2 when a cooperative factorisation gave up waiting
+    int* info = nullptr;                                        // status block: |= DQ_STATUS_COOP_QR when a cooperative factorisation gave up waiting
     double* pw = nullptr; long pw_stride = 0;                   // panel-pivoted QR (qr_panel.hip): sketch, clean reflector panel, T; >= qr_panel_work_doubles(n) per chain
     int* pivpos = nullptr; long pivpos_stride = 0;              // panel-pivoted QR: pivot position of every column (-1 = live), n per chain
 };
 long qr_panel_work_doubles(int n);
-bool qr_panel_ok(int n, const QrWork& w);   // n a multiple of 16 in [16, 1024] and the workspace present
 int launch_qr_panel_formq(QrWork w, Mat L, int n, int n_chains, hipStream_t s);   // explicit Q of that factorisation from its compact-WY factors (left in w.pw)
 int launch_qr_panel(Mat A, QrWork w, int n, int n_chains, hipStream_t s);   // qr_panel.hip: A -> reflectors / R0 in place, tau, jpvt (same format as the QRCP kernels)
 long qrcp_coop_sync_granules(int n);        // granules of cooperative-QRCP workspace per chain
 int qrcp_coop_workgroups(int n, int n_chains);
-int launch_to_ldr(Mat A, Mat L, Vec d, Mat R, QrWork w, int n, int n_chains, hipStream_t s);
+// the factorisation to_LDR runs on (chosen by pick_qr, engine.hip): panel-pivoted blocked QR (qr_panel.hip), column-owner QRCP on one
+// CU (qr_colown.hip, n <= 256), cooperative QRCP (qr_coop.hip, needs w.sync), single-workgroup streaming QRCP (qr.hip)
+enum class QrFamily { Panel, ColumnOwner, Cooperative, Streaming };
+int launch_to_ldr(QrFamily f, Mat A, Mat L, Vec d, Mat R, QrWork w, int n, int n_chains, hipStream_t s);
 
-// ---- lu.hip -----------------------------------------------------------------
-// In-place LU with partial pivoting of A[c] (P A = L U); perm (n ints per
-// chain): row r of P*A is row perm[r] of A.  logabsdet[c] (+)= sum log|u_ii|
-// when non-null.  *info |= 1 on a zero / NaN pivot.
-// rowpos: scratch of n ints per chain for the blocked path (null -> single-workgroup streaming kernel)
-int launch_lu(Mat A, int* perm, long perm_stride, double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, hipStream_t s,
-              int* rowpos = nullptr, long rowpos_stride = 0);
+// ---- lu_blocked.hip, lu.hip --------------------------------------------------
+// In-place blocked LU with partial pivoting of A[c] (P A = L U), n <= 1024; perm (n ints per
+// chain): row r of P*A is row perm[r] of A; rowpos: scratch of n ints per chain.  logabsdet[c]
+// (+)= sum log|u_ii| when non-null.  *info |= DQ_STATUS_PIVOT on a zero / NaN pivot.
+int launch_lu_blocked(Mat A, int* perm, long perm_stride, int* rowpos, long rowpos_stride, double* logabsdet, int accumulate_logdet,
+                      int* info, int n, int n_chains, hipStream_t s);
 // Solve A X = B with the factors above, n right-hand sides.
 //   mode 0: X holds B on entry, overwritten by the solution.
 //   mode 1: B = diag(dg); X is overwritten.
@@ -142,9 +151,9 @@ int launch_lu_solve(CMat LU, const int* perm, long perm_stride, Mat X, CVec dg, 
 int launch_tri_solve(CMat R, const int* perm, long perm_stride, Mat X, CVec dg, double* scratch, long scratch_stride, int n, int n_chains, hipStream_t s);
 
 // ---- lu_gj.hip ----------------------------------------------------------------
-// X = A^-1 B for n <= 256 by blocked Gauss-Jordan elimination with partial pivoting (no substitution phase); A and B
+// X = A^-1 B for n <= 1024 by blocked Gauss-Jordan elimination with partial pivoting (no substitution phase); A and B
 // are destroyed.  SA: n*n scratch per chain, tinv: 2048 doubles per chain, perm / rowpos: n ints per chain.
-// logabsdet (optional): (+)= log|det A|.  *info |= 1 on a zero / NaN pivot.
+// logabsdet (optional): (+)= log|det A|.  *info |= DQ_STATUS_PIVOT on a zero / NaN pivot.
 int launch_gj_solve(Mat A, Mat B, Mat X, Mat SA, double* tinv, int* perm, long perm_stride, int* rowpos, long rowpos_stride,
                     double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, hipStream_t s);
 
@@ -176,7 +185,7 @@ struct UpdateDesc {
     int slice_absent_tile = -1;               // debug (DQMC_DEBUG_SLICE_ABSENT): this flush workgroup leaves at once, as if it had never become resident
     int slice_absent_l = -1;                  // debug (DQMC_DEBUG_SLICE_ABSENT=<tile>:<slice>): only in the launch of that time slice (-1: in every launch)
     int slice_late_tile = -1, slice_late_us = 0;   // debug (DQMC_DEBUG_SLICE_LATE=<tile>:<us>): this flush workgroup sleeps that long before it checks in
-    int* info = nullptr;                      // |= 4 when a hand-off of the persistent slice kernel timed out
+    int* info = nullptr;                      // status block: |= DQ_STATUS_HANDOFF when a hand-off of a persistent slice kernel timed out
     int* acc_out; long acc_stride;            // per chain per slice accepted counts [chain][2*nt] (+ offset chosen by caller)
     int n, nt;
 };
@@ -199,9 +208,12 @@ static_assert(sizeof(SliceSync) == SLICE_SYNC_BYTES, "SliceSync layout");
 constexpr unsigned SLICE_EPOCH_LIMIT = 1u << 24;
 constexpr unsigned SLICE_SOLO_BIT = 1u << 30, SLICE_FINAL_BIT = 1u << 31;
 __host__ __device__ inline unsigned slice_tag(unsigned epoch, unsigned window) { return (epoch << 8) | window; }
-// one slice = reset + windows x (scan kernel, flush kernel)
-// *gt_kept (optional): 1 when the path taken keeps d.GT equal to G^T, 0 when it leaves GT behind (n > 256 on the scan / flush kernel pairs)
-int launch_update_slice(const UpdateDesc& d, int l, int acc_slot, int n_chains, hipStream_t s, int* gt_kept = nullptr);
+// the local update of one time slice (chosen per engine by pick_slice_path, engine.hip): the persistent single-launch kernel with the
+// delayed-update walk (update.hip, n <= 256) or the sub-matrix walk (update_sm.hip), both need d.slice_sync and keep d.GT = G^T; the
+// single-workgroup solo kernel (n <= 256); windows x (scan kernel, flush kernel), at n <= 256 keeping GT, optionally ending in one solo
+// launch that finishes the slice after four windows
+enum class SlicePath { PersistentWalk, PersistentSubmatrix, Solo, Pairs, PairsTailSolo };
+int launch_update_slice(SlicePath path, const UpdateDesc& d, int l, int acc_slot, int n_chains, hipStream_t s);
 // sub-matrix variant of the persistent single-launch slice kernel (update_sm.hip)
 int launch_update_slice_sm(const UpdateDesc& d, int l, int acc_slot, int n_chains, hipStream_t s);
 int slice_flush_workgroups(int n);        // flush workgroups per chain of the persistent slice kernels

@@ -43,6 +43,65 @@ int init_device_kernels(int device) {
 }
 
 // ---------------------------------------------------------------------------
+// Kernel families of to_LDR, the solves and the local update, decided here and nowhere else (the per-size instance inside a family
+// is chosen next to its kernel) from n, the chain count, the CU reservation and the switches (README.md, "Environment switches").
+// ---------------------------------------------------------------------------
+struct Switches { bool qr_panel, qr_streaming, walk_submatrix, lu_classic, slice_multikernel; };
+static const Switches& switches() {           // read once per process
+    static const Switches sw = [] {
+        const char* panel = getenv("DQMC_QR_PANEL");
+        return Switches{!(panel && atoi(panel) == 0), getenv("DQMC_QR_STREAMING") != nullptr, getenv("DQMC_WALK_SUBMATRIX") != nullptr,
+                        getenv("DQMC_LU_CLASSIC") != nullptr, getenv("DQMC_SLICE_MULTIKERNEL") != nullptr};
+    }();
+    return sw;
+}
+
+// n = 704 ... 1024: 8.4 / 11.7 / 12.0 ms per inv(I + F1 F2) call with Gauss-Jordan against 9.9 / 14.0 / 14.1 with the blocked LU.
+// Latency regime only: with many chains per launch the blocked LU + per-column substitution has the higher throughput
+// (128 chains, cfg 3: 458 ms per step against 483 ms with the single-wave panels)
+constexpr int GJ_MAX_N = 1024, GJ_MAX_CHAINS = 8;
+constexpr int TRI_MAX_N = 640;      // any number of chains (128 chains at cfg 3: 432.9 against 437.3 ms per step)
+
+// allow_panel = false: the caller has no panel workspace (the batched initialisation)
+static QrFamily pick_qr(int n, int chains, bool allow_panel) {
+    const Switches& sw = switches();
+    if (sw.qr_streaming) return QrFamily::Streaming;
+    // one global pivot decision per 16 columns instead of one per column; DQMC_QR_PANEL=0 keeps the column-pivoted kernels at every size
+    // (the only way to reach qr_colown / qr_coop at n = 64 .. 1024 with few chains)
+    if (allow_panel && sw.qr_panel && n >= 64 && n <= 1024 && n % 16 == 0 && chains <= 8) return QrFamily::Panel;
+    if (n <= 256) return QrFamily::ColumnOwner;
+    // the matrix does not fit one CU: ceil(n/32) cooperating workgroups while they fit the CU budget (co-residency), the
+    // single-workgroup streaming kernel otherwise (many chains per launch: every CU is busy with its own chain anyway)
+    return qrcp_coop_workgroups(n, chains) <= 200 ? QrFamily::Cooperative : QrFamily::Streaming;
+}
+
+struct KernelPlan {
+    QrFamily qr;
+    enum class Solve { GaussJordan, BlockedLu } solve;             // M^-1 RHS: lu_gj.hip / lu_blocked.hip + lu.hip
+    enum class Rinv { Blocked, PerColumn } rinv;                    // R^-1 D of one to_LDR factor: tri_solve.hip / lu.hip
+    static KernelPlan pick(int n, int chains) {
+        return KernelPlan{pick_qr(n, chains, true),
+                          n <= GJ_MAX_N && chains <= GJ_MAX_CHAINS && !switches().lu_classic ? Solve::GaussJordan : Solve::BlockedLu,
+                          n <= TRI_MAX_N ? Rinv::Blocked : Rinv::PerColumn};
+    }
+};
+
+// the local-update path of an engine (launch_update_slice, update.hip); reserved: the engine holds a CU reservation (slice_reserve)
+static SlicePath pick_slice_path(int n, int chains, bool reserved) {
+    const Switches& sw = switches();
+    const bool walk = n <= 256;                                     // the register-resident delayed-update walk fits
+    if (sw.slice_multikernel) return SlicePath::Pairs;
+    // sub-matrix updates at n <= 256 are opt-in: 211 us per cfg-3 slice against 138 us for the delayed-update walk -- the k x k algebra
+    // is a dependent chain on one wave per SIMD (860 clk per two-proposal pass, 1780 clk per accepted flip), see DESIGN.md
+    if (reserved) return walk && !sw.walk_submatrix ? SlicePath::PersistentWalk : SlicePath::PersistentSubmatrix;
+    if (!walk) return SlicePath::Pairs;
+    // measured (cfg 3, sweeps/s, solo vs pairs): 64 chains 166 / 214, 128 chains 251 / 275, 256 chains 324 / 307 -- a chain's own CU
+    // flushes slower than the whole chip does, so the solo kernel pays once there are enough chains to occupy every CU
+    return chains >= 224 ? SlicePath::Solo : SlicePath::PairsTailSolo;
+}
+static bool is_persistent(SlicePath p) { return p == SlicePath::PersistentWalk || p == SlicePath::PersistentSubmatrix; }
+
+// ---------------------------------------------------------------------------
 // Workspace + stable linear algebra on device (stablelinalg.cpp restated as
 // launch sequences).  Shared by the engine and the stateless ABI calls.
 // ---------------------------------------------------------------------------
@@ -67,8 +126,7 @@ struct Ctx {
     double* qpw = nullptr;                     // panel-pivoted QR (qr_panel.hip): qr_panel_work_doubles(n) * C
     int* qpivpos = nullptr;                    // ... and its pivot positions: n * C
     double* trinv = nullptr;                   // blocked triangular solve: inverses of the 16 x 16 diagonal blocks, 16 * (n + 16) * C
-    bool use_tri = false;                      // R^-1 D by tri_solve.hip (n <= 640; the per-column substitution of lu.hip above that)
-    bool use_gj = false;                       // n <= 1024, few chains: solves go through lu_gj.hip (DQMC_LU_CLASSIC=1 keeps dgetrf + dgetrs)
+    KernelPlan plan{};                         // the kernel families of this (n, C); each family's workspace above exists only when chosen
 
     Mat T(int k) const { return Mat{pool + (long)k * C * nn, nn}; }
     Vec V(int k) const { return Vec{vpool + (long)k * C * n, (long)n}; }
@@ -88,20 +146,11 @@ struct Ctx {
         DQ_HIP(hipMalloc(&vpool, sizeof(double) * 8 * C * n));
         DQ_HIP(hipMalloc(&ipool, sizeof(int) * (3L * C * n + 4)));
         DQ_HIP(hipMalloc(&spool, sizeof(double) * 4 * C));
-        DQ_HIP(hipMalloc(&qsync, sizeof(unsigned long long) * qrcp_coop_sync_granules(n) * C));
-        DQ_HIP(hipMalloc(&qabort, sizeof(int) * C));
-        DQ_HIP(hipMalloc(&tinv, sizeof(double) * 2048 * C));
-        DQ_HIP(hipMalloc(&trinv, sizeof(double) * 16 * (n + 16) * C));
-        if (n % 16 == 0 && n <= 1024) {
-            DQ_HIP(hipMalloc(&qpw, sizeof(double) * qr_panel_work_doubles(n) * C));
-            DQ_HIP(hipMalloc(&qpivpos, sizeof(int) * (size_t)n * C));
-        }
-        use_tri = n <= 640;     // any number of chains (128 chains at cfg 3: 432.9 against 437.3 ms per step)
-        // latency regime only: with many chains per launch the blocked LU + per-column substitution has the higher throughput
-        // (128 chains, cfg 3: 458 ms per step against 483 ms with the single-wave panels)
-        const int gj_max_chains = getenv("DQMC_GJ_MAX_CHAINS") ? atoi(getenv("DQMC_GJ_MAX_CHAINS")) : 8;
-        const int gj_max_n = getenv("DQMC_GJ_MAX_N") ? atoi(getenv("DQMC_GJ_MAX_N")) : 1024;     // test switch (256: blocked LU above); n = 704 ... 1024: 8.4 / 11.7 / 12.0 ms per inv(I + F1 F2) call against 9.9 / 14.0 / 14.1 with the blocked LU
-        use_gj = n <= gj_max_n && n <= 1024 && C <= gj_max_chains && getenv("DQMC_LU_CLASSIC") == nullptr;
+        plan = KernelPlan::pick(n, C);
+        if (plan.qr == QrFamily::Cooperative) { DQ_HIP(hipMalloc(&qsync, sizeof(unsigned long long) * qrcp_coop_sync_granules(n) * C)); DQ_HIP(hipMalloc(&qabort, sizeof(int) * C)); }
+        if (plan.qr == QrFamily::Panel) { DQ_HIP(hipMalloc(&qpw, sizeof(double) * qr_panel_work_doubles(n) * C)); DQ_HIP(hipMalloc(&qpivpos, sizeof(int) * (size_t)n * C)); }
+        if (plan.solve == KernelPlan::Solve::GaussJordan) DQ_HIP(hipMalloc(&tinv, sizeof(double) * 2048 * C));
+        if (plan.rinv == KernelPlan::Rinv::Blocked) DQ_HIP(hipMalloc(&trinv, sizeof(double) * 16 * (n + 16) * C));
         DQ_HIP(hipMemsetAsync(ipool, 0, sizeof(int) * (3L * C * n + 4), stream));
         return 0;
     }
@@ -132,16 +181,16 @@ struct Ctx {
         w.sync = qsync; w.sync_stride = qrcp_coop_sync_granules(n); w.abort_words = qabort; w.info = info();
         w.pw = qpw; w.pw_stride = qr_panel_work_doubles(n); w.pivpos = qpivpos; w.pivpos_stride = n;
         if (out.tri) *out.tri = keep;
-        return launch_to_ldr(A, out.L, out.d, out.R, w, n, C, stream);
+        return launch_to_ldr(plan.qr, A, out.L, out.d, out.R, w, n, C, stream);
     }
     // X = F.R^-1 diag(dinv): permuted triangular solve when F.R is a single QR factor, LU otherwise
     int r_inverse_scaled(LdrRef F, CVec dinv, Mat X, Mat lu_scratch) {
         if (F.tri && *F.tri && F.jpvt) {
-            if (use_tri) return launch_tri_solve(F.R, F.jpvt, n, X, dinv, trinv, 16L * (n + 16), n, C, stream);
+            if (plan.rinv == KernelPlan::Rinv::Blocked) return launch_tri_solve(F.R, F.jpvt, n, X, dinv, trinv, 16L * (n + 16), n, C, stream);
             return launch_lu_solve(F.R, F.jpvt, n, X, dinv, 2, n, C, stream);
         }
         DQ_TRY(launch_copy(F.R, lu_scratch, nn, C, stream));
-        DQ_TRY(launch_lu(lu_scratch, lperm(), n, nullptr, 0, info(), n, C, stream, rowpos(), n));
+        DQ_TRY(launch_lu_blocked(lu_scratch, lperm(), n, rowpos(), n, nullptr, 0, info(), n, C, stream));
         return launch_lu_solve(lu_scratch, lperm(), n, X, dinv, 1, n, C, stream);
     }
     // stablelinalg::mat_mul_ldr (source/stablelinalg.cpp:69-79): out = M * F   (uses T0,T1)
@@ -168,14 +217,14 @@ struct Ctx {
         DQ_TRY(gemm(F1.L, T(1), out.L));
         return gemm(T(2), F2.R, out.R);
     }
-    // Y = M^-1 RHS (arma::solve): blocked Gauss-Jordan for n <= 256 (result in T9's neighbour `out`), dgetrf + dgetrs otherwise
-    // (result overwrites RHS).  Returns the matrix holding Y in *Y.  M and RHS are destroyed.  (uses T9 as scratch)
+    // Y = M^-1 RHS (arma::solve): blocked Gauss-Jordan (result in `out`) or dgetrf + dgetrs (result overwrites RHS), as the plan says.
+    // Returns the matrix holding Y in *Y.  M and RHS are destroyed.  (uses T9 as scratch)
     int solve(Mat M, Mat RHS, Mat out, double* logdet_acc, Mat* Y) {
-        if (use_gj) {
+        if (plan.solve == KernelPlan::Solve::GaussJordan) {
             DQ_TRY(launch_gj_solve(M, RHS, out, T(9), tinv, lperm(), n, rowpos(), n, logdet_acc, 1, info(), n, C, stream));
             *Y = out; return 0;
         }
-        DQ_TRY(launch_lu(M, lperm(), n, logdet_acc, 1, info(), n, C, stream, rowpos(), n));
+        DQ_TRY(launch_lu_blocked(M, lperm(), n, rowpos(), n, logdet_acc, 1, info(), n, C, stream));
         DQ_TRY(launch_lu_solve(M, lperm(), n, RHS, CVec(), 0, n, C, stream));
         *Y = RHS; return 0;
     }
@@ -219,6 +268,34 @@ struct Ctx {
 // ---------------------------------------------------------------------------
 // Engine
 // ---------------------------------------------------------------------------
+// After a stream sync: read the status block (common.h), clear it, and report the first of its conditions in the order
+// HANDOFF, CENSUS, COOP_QR, PIVOT as DQMC_ENUMERIC.  *bits (optional) receives word 0.
+static int take_status(const Ctx& c, int* bits = nullptr) {
+    int w[4] = {0, 0, 0, 0};
+    DQ_HIP(hipMemcpy(w, c.info(), sizeof w, hipMemcpyDeviceToHost));
+    if (bits) *bits = w[0];
+    if (w[0] == 0) return 0;
+    (void)hipMemset(c.info(), 0, sizeof w);
+    if (w[0] & DQ_STATUS_HANDOFF) {
+        set_error("persistent slice kernel: a workgroup that had checked in stopped answering (device fault or pre-emption beyond the spin bound); the chain state is undefined -- set the fields again and call dqmc_init; this engine uses the scan / flush kernel pairs from now on");
+    } else if (w[0] & DQ_STATUS_CENSUS) {
+        // n > 256: the census of slice_sm_kernel failed at slice w[1] - 1.  That launch and (device-side latch, update_sm.hip) every later
+        // slice_sm_kernel launch enqueued behind it left their slices untouched; the wraps and stabilisations of the calls in flight ran.
+        char msg[640];
+        snprintf(msg, sizeof msg, "persistent sub-matrix slice kernel: its workgroups did not all become resident at time slice %d (device shared with other "
+                 "work?).  That slice and every later slice of the call(s) in flight proposed NOTHING (fields unchanged there, acceptance counts 0, their part of "
+                 "the random stream is spent); wraps and stabilisations ran, so fields, G and the stack are consistent with each other, but the sweep is not the "
+                 "one the stream describes from that slice on.  This engine uses the scan / flush kernel pairs from now on: restore the fields of the last "
+                 "completed sweep and call dqmc_init, or keep the state as a valid (shortened) sweep", w[1] - 1);
+        set_error(msg);
+    } else if (w[0] & DQ_STATUS_COOP_QR) {
+        set_error("cooperative QRCP gave up waiting for a partner workgroup (not co-resident?)");
+    } else {
+        set_error("LU factorisation hit a zero or NaN pivot");
+    }
+    return DQMC_ENUMERIC;
+}
+
 struct Engine {
     int n = 0, nt = 0, n_stab = 0, n_stack = 0, C = 1, device = 0;
     long nn = 0;
@@ -263,8 +340,8 @@ struct Engine {
     double* utMeasNow = nullptr; double* utMeasSum = nullptr; long long ut_meas_count = 0;     // [C][3][nt + 1][n] dynamical observables: last / bin sums
     long long meas_count = 0;                                    // measurements accumulated in meas_sum
     char* slice_sync = nullptr;                                  // [C][SLICE_SYNC_BYTES = 2 KiB] hand-off words of the persistent slice kernels (SliceSync, common.h)
-    bool persistent = false;                                     // holds a CU reservation for the single-launch slice kernel (slice_reserve)
-    bool handoff_failed = false;                                 // a hand-off of a persistent kernel timed out once: this engine stays on the kernel pairs from then on
+    bool reserved = false;                                       // holds a CU reservation for the single-launch slice kernels (slice_reserve)
+    SlicePath slice_path = SlicePath::Pairs;                     // the local-update path; lowered to the unreserved choice once a persistent kernel fails (sync_and_check)
     unsigned slice_epoch = 0;                                    // launches of the persistent slice kernel so far: the tag of its hand-off words (SliceSync, common.h)
     int slice_absent_l = -1;                                     // ...=<tile>:<slice>: only in the launch of that time slice
     int slice_late_tile = -1, slice_late_us = 0;                 // DQMC_DEBUG_SLICE_LATE=<tile>:<us>: that flush workgroup checks in only after <us> microseconds (test of a LATE arrival)
@@ -292,7 +369,7 @@ struct Engine {
 
     ~Engine() {
         if (s) (void)hipStreamSynchronize(s);
-        if (persistent) slice_release(device, n, C);
+        if (reserved) slice_release(device, n, C);
         for (auto& p : ev_pairs) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
         if (stage_free) (void)hipEventDestroy(stage_free);
         void* ptrs[] = {expKh, invexpKh, hwOut, utMeasNow, utMeasSum, utG[0], utG[1], utG[2], utTmp, utErr, utL[0], utL[1], utD[0], utD[1], utR[0], utR[1], utP[0], utP[1], meas_now, meas_sum, GT, slice_sync, prep, stackP, expK, invexpK, cb_partner, cb_par, fields, expv, invexpv, tabs, tab8, G, pg_eye, pg_ones, Gtmp, bb0, bb1, stackL, stackD, stackR, tmpL, tmpD, tmpR,
@@ -311,7 +388,8 @@ struct Engine {
         if (nt % n_stab != 0) loc_l_end[n_stack - 1] = nt % n_stab - 1;                    // source/dqmc.cpp:13-18
         g_host.assign(g, g + C); gamma_host.assign(gamma, gamma + 4); eta_host.assign(eta, eta + 4);
         DQ_TRY(ctx.init(n, C, device)); s = ctx.stream;
-        persistent = slice_reserve(device, n, C);
+        reserved = slice_reserve(device, n, C);
+        slice_path = pick_slice_path(n, C, reserved);
         if (const char* a = getenv("DQMC_DEBUG_SLICE_ABSENT")) { slice_absent_tile = atoi(a); if (const char* c = strchr(a, ':')) slice_absent_l = atoi(c + 1); }
         if (const char* a = getenv("DQMC_DEBUG_SLICE_LATE")) { slice_late_tile = atoi(a); if (const char* c = strchr(a, ':')) slice_late_us = atoi(c + 1); }
         DQ_TRY(dalloc(&expK, C * nn)); DQ_TRY(dalloc(&invexpK, C * nn));
@@ -457,7 +535,8 @@ struct Engine {
         }
         QrWork w{iTau, (long)n, ijp, (long)n};
         w.info = ctx.info();
-        DQ_TRY(launch_to_ldr(cur, Mat{iL, nn}, Vec{iD, (long)n}, Mat{iR, nn}, w, n, S, s));   // to_LDR(Bbar_i) for every block
+        // to_LDR(Bbar_i) for every block, S chains of the same choice as Ctx's minus the panel family (no panel workspace here)
+        DQ_TRY(launch_to_ldr(pick_qr(n, S, false), cur, Mat{iL, nn}, Vec{iD, (long)n}, Mat{iR, nn}, w, n, S, s));
         // stack[S - 1] = its own factorisation (R a single permuted-triangular factor), then the chain of products
         LdrRef last = stk(S - 1);
         DQ_TRY(launch_copy(CMat(iL + (size_t)(S - 1) * nn, nn), last.L, nn, 1, s));
@@ -523,11 +602,11 @@ struct Engine {
         return ctx.gemm(ctx.T(0), CMat(expK, nn), mG(), CVec(), ev(l), CVec(), 0, 0, use_gt() ? Mat{GT, nn} : Mat{nullptr, 0});
     }
     // the walk reads rows of G from a transposed copy: the register walk (n <= 256) and the persistent sub-matrix kernel (any n)
-    bool use_gt() const { return n <= 256 || (persistent && !handoff_failed); }     // n > 256: only the persistent sub-matrix kernel reads and maintains GT
+    bool use_gt() const { return n <= 256 || slice_path == SlicePath::PersistentSubmatrix; }     // n > 256: only the persistent sub-matrix kernel reads and maintains GT
     UpdateDesc udesc() const {
         UpdateDesc d; d.G = mG(); d.fields = fields; d.f_stride = (long)nt * n; d.expv = expv; d.invexpv = invexpv; d.v_stride = (long)nt * n;
         d.tabs = tabs; d.perm = rs_perm; d.kprop = rs_k; d.u = rs_u; d.rs_stride = (long)nt * n; d.Upanel = Upanel; d.Wpanel = Wpanel; d.Cpanel = Cpanel;
-        d.panel_stride = (long)UPDATE_KD * n; d.state = state; d.state_stride = 4; d.prep = prep; d.prep_stride = 4L * n; d.slice_sync = (persistent && !handoff_failed) ? slice_sync : nullptr; d.slice_epoch = slice_epoch; d.slice_absent_tile = slice_absent_tile; d.slice_absent_l = slice_absent_l; d.slice_late_tile = slice_late_tile; d.slice_late_us = slice_late_us; d.GT = Mat{GT, nn}; d.gt_valid = gt_valid ? 1 : 0; d.info = ctx.info(); d.acc_out = acc; d.acc_stride = nt; d.n = n; d.nt = nt;
+        d.panel_stride = (long)UPDATE_KD * n; d.state = state; d.state_stride = 4; d.prep = prep; d.prep_stride = 4L * n; d.slice_sync = is_persistent(slice_path) ? slice_sync : nullptr; d.slice_epoch = slice_epoch; d.slice_absent_tile = slice_absent_tile; d.slice_absent_l = slice_absent_l; d.slice_late_tile = slice_late_tile; d.slice_late_us = slice_late_us; d.GT = Mat{GT, nn}; d.gt_valid = gt_valid ? 1 : 0; d.info = ctx.info(); d.acc_out = acc; d.acc_stride = nt; d.n = n; d.nt = nt;
         return d;
     }
     int local_update(int l) {
@@ -537,13 +616,11 @@ struct Engine {
             e0 = ev_pairs[ev_used].first; e1 = ev_pairs[ev_used].second; ++ev_used;
             DQ_HIP(hipEventRecord(e0, s));
         }
-        if (persistent && !handoff_failed) {
+        if (is_persistent(slice_path)) {
             // every launch of a persistent slice kernel gets its own number: the hand-off words carry it, so none has to be re-armed
             if (++slice_epoch >= SLICE_EPOCH_LIMIT) { DQ_HIP(hipMemsetAsync(slice_sync, 0, (size_t)C * SLICE_SYNC_BYTES, s)); slice_epoch = 1; }
         }
-        int gt_kept = 1;
-        DQ_TRY(launch_update_slice(udesc(), l, l, C, s, &gt_kept));
-        if (!gt_kept) gt_valid = false;                               // n > 256 on the kernel pairs: the next persistent launch transposes first
+        DQ_TRY(launch_update_slice(slice_path, udesc(), l, l, C, s));
         if (profiling) DQ_HIP(hipEventRecord(e1, s));
         return 0;
     }
@@ -685,25 +762,13 @@ struct Engine {
             for (size_t k = 0; k < ev_used; ++k) { float ms = 0.f; DQ_HIP(hipEventElapsedTime(&ms, ev_pairs[k].first, ev_pairs[k].second)); upd_ms += ms; }
             upd_launches += (long long)ev_used; ev_used = 0;
         }
-        int h_info2[2] = {0, 0};
-        DQ_HIP(hipMemcpy(h_info2, ctx.info(), 2 * sizeof(int), hipMemcpyDeviceToHost));
-        const int h_info = h_info2[0];
-        if (h_info & 4) { handoff_failed = true; gt_valid = false; set_error("persistent slice kernel: a workgroup that had checked in stopped answering (device fault or pre-emption beyond the spin bound); the chain state is undefined -- set the fields again and call dqmc_init; this engine uses the scan / flush kernel pairs from now on"); (void)hipMemset(ctx.info(), 0, sizeof(int)); (void)hipMemset(slice_sync, 0, (size_t)C * SLICE_SYNC_BYTES); slice_epoch = 0; return DQMC_ENUMERIC; }
-        if (h_info & 8) {
-            // n > 256: the census of slice_sm_kernel failed at slice info[1] - 1.  That launch and (device-side latch, update_sm.hip) every later
-            // slice_sm_kernel launch enqueued behind it left their slices untouched; the wraps and stabilisations of the calls in flight ran.
-            handoff_failed = true; gt_valid = false;
-            char msg[640];
-            snprintf(msg, sizeof msg, "persistent sub-matrix slice kernel: its workgroups did not all become resident at time slice %d (device shared with other "
-                     "work?).  That slice and every later slice of the call(s) in flight proposed NOTHING (fields unchanged there, acceptance counts 0, their part of "
-                     "the random stream is spent); wraps and stabilisations ran, so fields, G and the stack are consistent with each other, but the sweep is not the "
-                     "one the stream describes from that slice on.  This engine uses the scan / flush kernel pairs from now on: restore the fields of the last "
-                     "completed sweep and call dqmc_init, or keep the state as a valid (shortened) sweep", h_info2[1] - 1);
-            set_error(msg); (void)hipMemset(ctx.info(), 0, 2 * sizeof(int)); return DQMC_ENUMERIC;
+        int bits = 0;
+        const int rc = take_status(ctx, &bits);
+        if (bits & (DQ_STATUS_HANDOFF | DQ_STATUS_CENSUS)) {        // a persistent slice kernel failed: the kernel pairs from now on
+            slice_path = pick_slice_path(n, C, false); gt_valid = false;
+            if (bits & DQ_STATUS_HANDOFF) { (void)hipMemset(slice_sync, 0, (size_t)C * SLICE_SYNC_BYTES); slice_epoch = 0; }
         }
-        if (h_info & 2) { set_error("cooperative QRCP gave up waiting for a partner workgroup (not co-resident?)"); (void)hipMemset(ctx.info(), 0, sizeof(int)); return DQMC_ENUMERIC; }
-        if (h_info) { set_error("LU factorisation hit a zero or NaN pivot"); (void)hipMemset(ctx.info(), 0, sizeof(int)); return DQMC_ENUMERIC; }
-        return 0;
+        return rc;
     }
 };
 
@@ -742,10 +807,7 @@ static int download_ldr(Ctx* c, LdrRef f, double* L, double* d, double* R) {
     DQ_HIP(hipMemcpyAsync(R, f.R.p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
     DQ_HIP(hipMemcpyAsync(d, f.d.p, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream));
     DQ_HIP(hipStreamSynchronize(c->stream));
-    int h_info = 0;
-    DQ_HIP(hipMemcpy(&h_info, c->info(), sizeof(int), hipMemcpyDeviceToHost));
-    if (h_info) { set_error("factorisation hit a zero or NaN pivot"); (void)hipMemset(c->info(), 0, sizeof(int)); return DQMC_ENUMERIC; }
-    return 0;
+    return take_status(*c);
 }
 static LdrRef slot(Ctx* c, double* extra, int k) {     // k = 0,1,2: LDR-sized scratch slots after the two upload slots
     double* base = extra + (long)k * (2 * c->nn + c->n);
@@ -822,9 +884,7 @@ int dqmc_inv_I_plus_ldr(int n, const double* L, const double* d, const double* R
     DQ_HIP(hipMemcpyAsync(&ld, c->scal(1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
     DQ_HIP(hipStreamSynchronize(c->stream));
     if (logdet) *logdet = ld;
-    int h_info = 0; DQ_HIP(hipMemcpy(&h_info, c->info(), sizeof(int), hipMemcpyDeviceToHost));
-    if (h_info) { set_error("LU hit a zero or NaN pivot"); (void)hipMemset(c->info(), 0, sizeof(int)); return DQMC_ENUMERIC; }
-    return 0;
+    return take_status(*c);
 }
 int dqmc_inv_I_plus_ldr_mul_ldr(int n, const double* L1, const double* d1, const double* R1, const double* L2, const double* d2, const double* R2, double* G) {
     API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
@@ -832,9 +892,7 @@ int dqmc_inv_I_plus_ldr_mul_ldr(int n, const double* L1, const double* d1, const
     DQ_TRY(c->inv_I_plus_ldr_mul_ldr(F1, F2, c->T(6)));
     DQ_HIP(hipMemcpyAsync(G, c->T(6).p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
     DQ_HIP(hipStreamSynchronize(c->stream));
-    int h_info = 0; DQ_HIP(hipMemcpy(&h_info, c->info(), sizeof(int), hipMemcpyDeviceToHost));
-    if (h_info) { set_error("LU hit a zero or NaN pivot"); (void)hipMemset(c->info(), 0, sizeof(int)); return DQMC_ENUMERIC; }
-    return 0;
+    return take_status(*c);
 }
 int dqmc_gemm(int n, const double* A, int transA, const double* B, int transB, double* Cm) {
     API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
@@ -1102,8 +1160,8 @@ int dqmc_update_kernel_time(dqmc_engine* h, double* ms, int64_t* n_launches, int
     e.upd_ms = 0.0; e.upd_launches = 0; e.upd_accept_base = acc;
     return 0;
 }
-// diagnostic: 1 when the next local update of this engine takes a persistent single-launch slice kernel (it holds a CU reservation
-// and no hand-off has failed), 0 for the kernel pairs
+// diagnostic: 1 when the next local update of this engine takes a persistent single-launch slice kernel (Engine::slice_path), 0 for
+// the kernel pairs and the solo kernel
 int dqmc_debug_snapshot(dqmc_engine* h, double* wrap_err, int* accepted, unsigned int* sync_words, unsigned int* slice_epoch) {
     CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
     DQ_HIP(hipStreamSynchronize(e.s));
@@ -1116,7 +1174,7 @@ int dqmc_debug_snapshot(dqmc_engine* h, double* wrap_err, int* accepted, unsigne
 int dqmc_slice_path(dqmc_engine* h) {
     if (!h) return -1;
     Engine& e = h->e;
-    if (!(e.persistent && !e.handoff_failed)) return 0;
+    if (!is_persistent(e.slice_path)) return 0;
     // 2: at least one launch of the persistent kernel fell back to the solo walk (a flush workgroup had not become resident in time)
     unsigned solo = 0;
     for (int c = 0; c < e.C && !solo; ++c) {

@@ -147,16 +147,6 @@ __global__ __launch_bounds__(256) void lu_solve_kernel(CMat LUm, const int* perm
     }
 }
 
-int launch_lu_blocked(Mat A, int* perm, long perm_stride, int* rowpos, long rowpos_stride, double* logabsdet, int accumulate_logdet,
-                      int* info, int n, int n_chains, hipStream_t s);     // lu_blocked.hip
-
-int launch_lu(Mat A, int* perm, long perm_stride, double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, hipStream_t s,
-              int* rowpos, long rowpos_stride) {
-    if (n > 1024) { set_error("LU kernel supports n <= 1024"); return -1; }
-    if (!rowpos) { set_error("LU: row-position workspace missing"); return -1; }
-    return launch_lu_blocked(A, perm, perm_stride, rowpos, rowpos_stride, logabsdet, accumulate_logdet, info, n, n_chains, s);
-}
-
 template <int NR>
 static int launch_solve_nr(CMat LU, const int* perm, long ps, Mat X, CVec dg, int mode, int n, int n_chains, hipStream_t s) {
     if (n_chains <= 4) hipLaunchKernelGGL((lu_solve_kernel<NR, 1>), dim3((n + 3) / 4, n_chains), dim3(256), 0, s, LU, perm, ps, X, dg, mode, n);

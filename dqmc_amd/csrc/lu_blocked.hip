@@ -98,7 +98,7 @@ __global__ __launch_bounds__(1024) void lu_panel_kernel(Mat Am, int* perm_p, lon
         const bool bad = __any(!(pv > 0.0));
         if (lane == 0) {
             if (logabsdet) logabsdet[chain] = ((accumulate || k0 > 0) ? logabsdet[chain] : 0.0) + ls;
-            if (info && bad) atomicOr(info, 1);
+            if (info && bad) atomicOr(info, DQ_STATUS_PIVOT);
         }
     }
 }

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(64) void gj_panel_kernel(CMat Am, int* rowpos_p, lo
         const double ls = wave_sum(log(pv));
         if (lane == 0) {
             if (logabsdet) logabsdet[chain] = ((accumulate || k0 > 0) ? logabsdet[chain] : 0.0) + ls;
-            if (info && (singular || !(ls == ls))) atomicOr(info, 1);
+            if (info && (singular || !(ls == ls))) atomicOr(info, DQ_STATUS_PIVOT);
         }
     }
     // The four 16 x 16 triangular inverses, one column per lane (lane = 16 * block + column): unit-lower blocks by forward
@@ -184,7 +184,7 @@ __device__ __forceinline__ void gj_panel_logdet(double (&LU)[GJ_NB][GJ_NB], doub
     const double ls = wave_sum(log(pv));
     if (lane == 0) {
         if (logabsdet) logabsdet[chain] = ((accumulate || k0 > 0) ? logabsdet[chain] : 0.0) + ls;
-        if (info && (s_sing || !(ls == ls))) atomicOr(info, 1);
+        if (info && (s_sing || !(ls == ls))) atomicOr(info, DQ_STATUS_PIVOT);
     }
 }
 template <int... Js>
@@ -535,8 +535,8 @@ __global__ __launch_bounds__(256) void gj_update_kernel(Mat Am, Mat Bm, Mat SAm,
         if (st_ok[reg]) dst[row0 + kk + 4 * reg + coff] = cold[reg] - acc[reg];
 }
 
-// X = A^-1 B (n <= 256).  A and B are destroyed; SA: n*n scratch per chain; tinv: 2048 doubles per chain;
-// perm / rowpos: n ints per chain.  logabsdet (optional) receives (+)= log|det A|; *info |= 1 on a zero / NaN pivot.
+// X = A^-1 B (n <= 1024).  A and B are destroyed; SA: n*n scratch per chain; tinv: 2048 doubles per chain;
+// perm / rowpos: n ints per chain.  logabsdet (optional) receives (+)= log|det A|; *info |= DQ_STATUS_PIVOT on a zero / NaN pivot.
 int launch_gj_solve(Mat A, Mat B, Mat X, Mat SA, double* tinv, int* perm, long perm_stride, int* rowpos, long rowpos_stride,
                     double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, hipStream_t s) {
     if (n > 1024) { set_error("gj_solve supports n <= 1024"); return -1; }

@@ -350,39 +350,6 @@ __global__ void assemble_r_kernel(CMat Am, const int* jpvt_p, long jpvt_stride, 
     if (threadIdx.x == 0) d[j] = fabs(A[j + (long)n * col]);
 }
 
-int launch_qrcp_coop(Mat A, QrWork w, int n, int n_chains, hipStream_t s);     // qr_coop.hip
-int launch_qrcp_colown(Mat A, QrWork w, int n, int n_chains, hipStream_t s);   // qr_colown.hip
-
-// NRSEL = 0: on-chip QRCP (n <= 256: the single-CU column-owner kernel); -1: P cooperating workgroups (n > 256);
-// otherwise the single-workgroup streaming kernel with NRSEL rows per lane
-template <int NRSEL>
-static int launch_to_ldr_nr(Mat A, Mat L, Vec d, Mat R, QrWork w, int n, int n_chains, hipStream_t s) {
-    constexpr int NR = NRSEL <= 0 ? 4 : NRSEL;
-    if (NRSEL <= 0) {
-        if (NRSEL == -2) DQ_TRY_RC(launch_qr_panel(A, w, n, n_chains, s));
-        else if (NRSEL == 0) DQ_TRY_RC(launch_qrcp_colown(A, w, n, n_chains, s));
-        else DQ_TRY_RC(launch_qrcp_coop(A, w, n, n_chains, s));
-        if (NRSEL == -2) DQ_TRY_RC(launch_qr_panel_formq(w, L, n, n_chains, s));
-        else if (formq_blocked_ok(n)) launch_formq_blocked(CMat(A), w, L, n, n_chains, s);
-        else if (n <= 256) hipLaunchKernelGGL((formq_kernel<16>), dim3((n + 15) / 16, n_chains), dim3(256), 0, s, CMat(A), (const double*)w.tau, w.tau_stride,
-                                              (const int*)w.jpvt, w.jpvt_stride, L, n);
-        else if (n <= 576) hipLaunchKernelGGL((formq_kernel<36>), dim3((n + 15) / 16, n_chains), dim3(256), 0, s, CMat(A), (const double*)w.tau, w.tau_stride,
-                                              (const int*)w.jpvt, w.jpvt_stride, L, n);
-        else hipLaunchKernelGGL((formq_kernel<64>), dim3((n + 15) / 16, n_chains), dim3(256), 0, s, CMat(A), (const double*)w.tau, w.tau_stride,
-                                (const int*)w.jpvt, w.jpvt_stride, L, n);
-        hipLaunchKernelGGL(assemble_r_kernel, dim3(n, n_chains), dim3(128), 0, s, CMat(A), (const int*)w.jpvt, w.jpvt_stride, d, R, n);
-        DQ_HIP(hipGetLastError());
-        return 0;
-    }
-    const size_t lds = sizeof(double) * ((size_t)3 * n + (size_t)16 * n + 32) + sizeof(int) * (16 + (size_t)n) + 64;
-    hipLaunchKernelGGL((qrcp_kernel<NR>), dim3(1, n_chains), dim3(1024), lds, s, A, w, n);
-    hipLaunchKernelGGL((formq_kernel<4 * NR>), dim3((n + 15) / 16, n_chains), dim3(256), 0, s, CMat(A), (const double*)w.tau, w.tau_stride,
-                       (const int*)w.jpvt, w.jpvt_stride, L, n);
-    hipLaunchKernelGGL(assemble_r_kernel, dim3(n, n_chains), dim3(128), 0, s, CMat(A), (const int*)w.jpvt, w.jpvt_stride, d, R, n);
-    DQ_HIP(hipGetLastError());
-    return 0;
-}
-
 int qr_init_device() {
     DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(qrcp_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(qrcp_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -392,23 +359,61 @@ int qr_init_device() {
     return 0;
 }
 
-int launch_to_ldr(Mat A, Mat L, Vec d, Mat R, QrWork w, int n, int n_chains, hipStream_t s) {
+int launch_qrcp_coop(Mat A, QrWork w, int n, int n_chains, hipStream_t s);     // qr_coop.hip
+int launch_qrcp_colown(Mat A, QrWork w, int n, int n_chains, hipStream_t s);   // qr_colown.hip
+
+// d, R of a factorisation left in A / w.jpvt (every family)
+static int launch_assemble_r(Mat A, Vec d, Mat R, const QrWork& w, int n, int n_chains, hipStream_t s) {
+    hipLaunchKernelGGL(assemble_r_kernel, dim3(n, n_chains), dim3(128), 0, s, CMat(A), (const int*)w.jpvt, w.jpvt_stride, d, R, n);
+    DQ_HIP(hipGetLastError());
+    return 0;
+}
+// explicit Q, d and R of a column-pivoted factorisation (column-owner or cooperative QRCP) left in A / w
+static int formq_assemble(Mat A, Mat L, Vec d, Mat R, const QrWork& w, int n, int n_chains, hipStream_t s) {
+    if (formq_blocked_ok(n)) launch_formq_blocked(CMat(A), w, L, n, n_chains, s);
+    else if (n <= 256) hipLaunchKernelGGL((formq_kernel<16>), dim3((n + 15) / 16, n_chains), dim3(256), 0, s, CMat(A), (const double*)w.tau, w.tau_stride,
+                                          (const int*)w.jpvt, w.jpvt_stride, L, n);
+    else if (n <= 576) hipLaunchKernelGGL((formq_kernel<36>), dim3((n + 15) / 16, n_chains), dim3(256), 0, s, CMat(A), (const double*)w.tau, w.tau_stride,
+                                          (const int*)w.jpvt, w.jpvt_stride, L, n);
+    else hipLaunchKernelGGL((formq_kernel<64>), dim3((n + 15) / 16, n_chains), dim3(256), 0, s, CMat(A), (const double*)w.tau, w.tau_stride,
+                            (const int*)w.jpvt, w.jpvt_stride, L, n);
+    return launch_assemble_r(A, d, R, w, n, n_chains, s);
+}
+static int to_ldr_panel(Mat A, Mat L, Vec d, Mat R, const QrWork& w, int n, int n_chains, hipStream_t s) {
+    DQ_TRY_RC(launch_qr_panel(A, w, n, n_chains, s));
+    DQ_TRY_RC(launch_qr_panel_formq(w, L, n, n_chains, s));
+    return launch_assemble_r(A, d, R, w, n, n_chains, s);
+}
+// the single-workgroup streaming kernel with NR rows per lane
+template <int NR>
+static int to_ldr_streaming(Mat A, Mat L, Vec d, Mat R, const QrWork& w, int n, int n_chains, hipStream_t s) {
+    const size_t lds = sizeof(double) * ((size_t)3 * n + (size_t)16 * n + 32) + sizeof(int) * (16 + (size_t)n) + 64;
+    hipLaunchKernelGGL((qrcp_kernel<NR>), dim3(1, n_chains), dim3(1024), lds, s, A, w, n);
+    hipLaunchKernelGGL((formq_kernel<4 * NR>), dim3((n + 15) / 16, n_chains), dim3(256), 0, s, CMat(A), (const double*)w.tau, w.tau_stride,
+                       (const int*)w.jpvt, w.jpvt_stride, L, n);
+    return launch_assemble_r(A, d, R, w, n, n_chains, s);
+}
+
+int launch_to_ldr(QrFamily f, Mat A, Mat L, Vec d, Mat R, QrWork w, int n, int n_chains, hipStream_t s) {
     if (n > 1024) { set_error("to_LDR kernel supports n <= 1024"); return -1; }
-    static const bool force_stream = getenv("DQMC_QR_STREAMING") != nullptr;    // A/B switch for tests and profiling
-    // panel-pivoted blocked QR (qr_panel.hip): one global pivot decision per 16 columns instead of one per column.  DQMC_QR_PANEL=0 keeps the
-    // column-pivoted kernels at every size (test switch: the only way to reach qr_colown / qr_coop at n = 64 .. 1024 with few chains)
-    static const bool use_panel = !(getenv("DQMC_QR_PANEL") && atoi(getenv("DQMC_QR_PANEL")) == 0);
-    if (use_panel && !force_stream && n >= 64 && n_chains <= 8 && qr_panel_ok(n, w)) return launch_to_ldr_nr<-2>(A, L, d, R, w, n, n_chains, s);
-    if (n <= 256 && !force_stream) return launch_to_ldr_nr<0>(A, L, d, R, w, n, n_chains, s);
-    // n > 256: the matrix does not fit one CU; ceil(n/32) cooperating workgroups while they fit the CU budget (co-residency), the
-    // single-workgroup streaming kernel otherwise (many chains per launch: every CU is busy with its own chain anyway)
-    if (n > 256 && !force_stream && w.sync && w.sync_stride >= qrcp_coop_sync_granules(n) && qrcp_coop_workgroups(n, n_chains) <= 200)
-        return launch_to_ldr_nr<-1>(A, L, d, R, w, n, n_chains, s);
-    if (n <= 64) return launch_to_ldr_nr<1>(A, L, d, R, w, n, n_chains, s);
-    if (n <= 128) return launch_to_ldr_nr<2>(A, L, d, R, w, n, n_chains, s);
-    if (n <= 256) return launch_to_ldr_nr<4>(A, L, d, R, w, n, n_chains, s);
-    if (n <= 576) return launch_to_ldr_nr<9>(A, L, d, R, w, n, n_chains, s);
-    return launch_to_ldr_nr<16>(A, L, d, R, w, n, n_chains, s);
+    switch (f) {
+    case QrFamily::Panel: return to_ldr_panel(A, L, d, R, w, n, n_chains, s);
+    case QrFamily::ColumnOwner:
+        if (n > 256) break;
+        DQ_TRY_RC(launch_qrcp_colown(A, w, n, n_chains, s));
+        return formq_assemble(A, L, d, R, w, n, n_chains, s);
+    case QrFamily::Cooperative:
+        DQ_TRY_RC(launch_qrcp_coop(A, w, n, n_chains, s));
+        return formq_assemble(A, L, d, R, w, n, n_chains, s);
+    case QrFamily::Streaming:
+        if (n <= 64) return to_ldr_streaming<1>(A, L, d, R, w, n, n_chains, s);
+        if (n <= 128) return to_ldr_streaming<2>(A, L, d, R, w, n, n_chains, s);
+        if (n <= 256) return to_ldr_streaming<4>(A, L, d, R, w, n, n_chains, s);
+        if (n <= 576) return to_ldr_streaming<9>(A, L, d, R, w, n, n_chains, s);
+        return to_ldr_streaming<16>(A, L, d, R, w, n, n_chains, s);
+    }
+    set_error("to_LDR: kernel family not available at this n");
+    return -1;
 }
 
 }  // namespace dq

@@ -198,11 +198,11 @@ __global__ __launch_bounds__(QC_T) void qrcp_coop_kernel(Mat Am, QrWork w, int n
                 const bool all_ok = __all(ok);
                 // bounded spin: give up, raise the chain's abort word (every later spin of every workgroup then exits at
                 // once) and carry on with whatever was read -- the barrier structure stays intact, the kernel ends in
-                // bounded time, the host sees info bit 1 and reports the factorisation as failed
+                // bounded time, the host sees DQ_STATUS_COOP_QR and reports the factorisation as failed
                 bool bail = false;
                 if (!all_ok && (++spins > QC_SPIN_LIMIT || __hip_atomic_load(abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
                     __hip_atomic_store(abort_w, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (info && lane == 0) atomicOr(info, 2);
+                    if (info && lane == 0) atomicOr(info, DQ_STATUS_COOP_QR);
                     bail = true;
                 }
                 if (all_ok || bail) {
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(QC_T) void qrcp_coop_kernel(Mat Am, QrWork w, int n
                 if (__all(ok)) break;
                 if (++spins > QC_SPIN_LIMIT || __hip_atomic_load(abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
                     __hip_atomic_store(abort_w, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (info && lane == 0) atomicOr(info, 2);
+                    if (info && lane == 0) atomicOr(info, DQ_STATUS_COOP_QR);
                     break;
                 }
                 __builtin_amdgcn_s_sleep(1);

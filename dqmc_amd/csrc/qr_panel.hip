@@ -610,7 +610,8 @@ int launch_qr_panel_formq(QrWork w, Mat L, int n, int n_chains, hipStream_t s) {
     return 0;
 }
 
-bool qr_panel_ok(int n, const QrWork& w) { return n >= 16 && n <= 1024 && n % 16 == 0 && w.pw != nullptr && w.pivpos != nullptr && w.pw_stride >= qr_panel_work_doubles(n); }
+// argument guard of launch_qr_panel: n a multiple of 16 in [16, 1024] and the workspace present
+static bool qr_panel_ok(int n, const QrWork& w) { return n >= 16 && n <= 1024 && n % 16 == 0 && w.pw != nullptr && w.pivpos != nullptr && w.pw_stride >= qr_panel_work_doubles(n); }
 long qr_panel_work_doubles(int n) { return (long)(QP_SR + 2 * n) * n + (long)QP_B * n; }   // Y | V panels | T factors | V panels row-major
 
 int launch_qr_panel(Mat A, QrWork w, int n, int n_chains, hipStream_t s) {

@@ -273,7 +273,7 @@ __device__ __forceinline__ void slice_wait_arrivals(SliceSync* sy, unsigned epoc
             if (++spins > SLICE_SPIN_LIMIT) { broken = true; break; }
             __builtin_amdgcn_s_sleep(1);
         }
-        if (broken && lane == 0) { __hip_atomic_store(&sy->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (info) atomicOr(info, 4); }
+        if (broken && lane == 0) { __hip_atomic_store(&sy->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (info) atomicOr(info, DQ_STATUS_HANDOFF); }
     }
     __syncthreads();
 }
@@ -769,7 +769,7 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, S
                     if (++spins > SLICE_SPIN_LIMIT) { give_up = true; break; }
                     __builtin_amdgcn_s_sleep(1);
                 }
-                if (give_up && lane == 0) { __hip_atomic_store(&sy->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (info) atomicOr(info, 4); }
+                if (give_up && lane == 0) { __hip_atomic_store(&sy->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (info) atomicOr(info, DQ_STATUS_HANDOFF); }
                 if (lane == 0) bcast[win & 1] = give_up ? ~0ULL : word;
             }
             __syncthreads();
@@ -972,30 +972,23 @@ int update_init_device() {
     return 0;
 }
 
-int launch_update_slice(const UpdateDesc& d, int l, int acc_slot, int n_chains, hipStream_t s, int* gt_kept) {
+int launch_update_slice(SlicePath path, const UpdateDesc& d, int l, int acc_slot, int n_chains, hipStream_t s) {
     const int n = d.n;
-    if (gt_kept) *gt_kept = 1;
     if (n > 1024) { set_error("local update kernel supports n_sites <= 1024"); return -1; }
     const int kd = pick_kd(n);
     const int threads = ((n + 63) / 64) * 64;
     const bool regs = threads <= 256;                               // walk v3 (register-resident pending pairs, needs GT)
     const size_t lds = scan_lds_bytes(n, kd, regs);
     const int tiles = (n + 31) / 32;
-    if (regs) {
+    if (!regs && path != SlicePath::Pairs && path != SlicePath::PersistentSubmatrix) { set_error("local update: the walk kernels of update.hip need n_sites <= 256"); return -1; }
+    if (regs || path == SlicePath::PersistentSubmatrix) {          // the walk reads rows of G from GT
         if (!d.GT.p) { set_error("local update: transposed workspace missing"); return -1; }
         if (!d.gt_valid) { if (int rc = launch_transpose_scale(CMat(d.G.p, d.G.stride), d.GT, CVec(), n, n_chains, s)) return rc; }      // GT = G^T, kept in step by the flushes
     }
-    static const bool multi_kernel = getenv("DQMC_SLICE_MULTIKERNEL") != nullptr;      // A/B switch
-    // persistent single-launch path: needs every workgroup of a chain resident at once, one per CU (the walk's LDS)
-    // sub-matrix updates (update_sm.hip): the same Markov chain from k x k algebra per proposal instead of 2 n k flops per accepted flip.
-    // Opt-in: measured 211 us per cfg-3 slice against 138 us for the delayed-update walk below -- the k x k algebra is a dependent chain
-    // on one wave per SIMD (860 clk per two-proposal pass, 1780 clk per accepted flip), see DESIGN.md
-    static const bool submatrix_walk = getenv("DQMC_WALK_SUBMATRIX") != nullptr;
-    if (!multi_kernel && d.slice_sync && d.Cpanel && d.GT.p && (submatrix_walk || !regs)) {       // n > 256: the default (see update_sm.hip)
-        if (!regs && !d.gt_valid) { if (int rc = launch_transpose_scale(CMat(d.G.p, d.G.stride), d.GT, CVec(), n, n_chains, s)) return rc; }
-        return launch_update_slice_sm(d, l, acc_slot, n_chains, s);
-    }
-    if (!multi_kernel && regs && d.slice_sync) {                    // slice_sync is only handed out with a CU reservation (slice_reserve)
+    switch (path) {
+    case SlicePath::PersistentSubmatrix: return launch_update_slice_sm(d, l, acc_slot, n_chains, s);     // sub-matrix updates (update_sm.hip)
+    case SlicePath::PersistentWalk:                                 // persistent single-launch kernel: every workgroup of a chain resident at once
+        if (!d.slice_sync) { set_error("persistent slice kernel: hand-off words missing"); return -1; }
         if (n == 256 && kd == UPDATE_KD)
             hipLaunchKernelGGL((slice_kernel<256, UPDATE_KD>), dim3(1 + tiles * tiles, n_chains), dim3(256), lds, s, d, reinterpret_cast<SliceSync*>(d.slice_sync), l, acc_slot, kd,
                                tiles, d.info);
@@ -1004,25 +997,22 @@ int launch_update_slice(const UpdateDesc& d, int l, int acc_slot, int n_chains, 
                                tiles, d.info);
         DQ_HIP(hipGetLastError());
         return 0;
-    }
-    // measured (cfg 3, sweeps/s, solo vs pairs): 64 chains 166 / 214, 128 chains 251 / 275, 256 chains 324 / 307 -- a chain's own CU
-    // flushes slower than the whole chip does, so the solo kernel pays once there are enough chains to occupy every CU
-    if (regs && !multi_kernel && n_chains >= 224) {
+    case SlicePath::Solo:
         hipLaunchKernelGGL(slice_solo_kernel, dim3(1, n_chains), dim3(256), lds, s, d, l, acc_slot, kd, 0);
         DQ_HIP(hipGetLastError());
         return 0;
+    case SlicePath::Pairs: case SlicePath::PairsTailSolo: break;
     }
     int windows = (n + kd - 1) / kd;
     // a thermalised slice ends after ~4 windows; the scan / flush pairs past that point are launches that find nothing to do (8 of 16
     // at cfg 3).  Four pairs, then ONE solo launch that finishes whatever a chain has left (usually nothing: it exits at once).
-    const bool tail_solo = regs && !multi_kernel && windows > 4;
+    const bool tail_solo = path == SlicePath::PairsTailSolo && windows > 4;
     if (tail_solo) windows = 4;
     for (int w = 0; w < windows; ++w) {
         if (regs) {
             hipLaunchKernelGGL(scan_kernel<256>, dim3(1, n_chains), dim3(threads), lds, s, d, l, acc_slot, w == 0 ? 1 : 0, kd);
             hipLaunchKernelGGL(flush_kernel<true>, dim3(tiles * tiles, n_chains), dim3(256), 0, s, d, tiles, kd);
-        } else {
-            if (gt_kept) *gt_kept = 0;                                                 // flush_kernel<false> updates G only
+        } else {                                                    // flush_kernel<false> updates G only: GT falls behind
             hipLaunchKernelGGL(scan_kernel<1024>, dim3(1, n_chains), dim3(threads), lds, s, d, l, acc_slot, w == 0 ? 1 : 0, kd);
             hipLaunchKernelGGL(flush_kernel<false>, dim3(tiles * tiles, n_chains), dim3(256), 0, s, d, tiles, kd);
         }

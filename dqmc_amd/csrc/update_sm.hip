@@ -481,7 +481,7 @@ __global__ __launch_bounds__(256) void slice_sm_kernel(UpdateDesc d, SliceSync* 
                     if (++spins > SM_SPIN_LIMIT) { give_up = true; break; }
                     __builtin_amdgcn_s_sleep(1);
                 }
-                if (give_up && lane == 0) { __hip_atomic_store(&sy->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (info) atomicOr(info, 4); }
+                if (give_up && lane == 0) { __hip_atomic_store(&sy->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (info) atomicOr(info, DQ_STATUS_HANDOFF); }
                 if (lane == 0) bcast[win & 1] = give_up ? ~0ULL : w_;
             }
             __syncthreads();
@@ -531,13 +531,13 @@ __global__ __launch_bounds__(256) void slice_sm_kernel(UpdateDesc d, SliceSync* 
         if (t < 32) sh.tl[t] = tab_g[t];
         // census BEFORE the first window (nothing has been modified yet): has every flush workgroup checked in for this launch?  If some
         // have not after a bounded wait, the walk publishes the abort flag and leaves: the slice stays exactly as it was (fields, exp(V)
-        // tables and G untouched), info |= 8 tells the host, the engine takes the kernel pairs from then on.  Once all have checked in,
+        // tables and G untouched), DQ_STATUS_CENSUS tells the host, the engine takes the kernel pairs from then on.  Once all have checked in,
         // every later hand-off completes in bounded time (resident workgroups always make progress).
-        // latch: once a slice of this engine has been abandoned (info & 8), no later launch of the same sweep may update either -- the sweep
+        // latch: once a slice of this engine has been abandoned (DQ_STATUS_CENSUS), no later launch of the same sweep may update either -- the sweep
         // would otherwise contain a slice that proposed nothing between slices that did, a trajectory that belongs to no Markov chain the
         // caller asked for.  Later launches publish the abort word at once (no census wait) and leave; the host reports the first
-        // abandoned slice (info[1]) and what state the engine is in (engine.hip: sync_and_check).
-        const bool latched = info && (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 8);
+        // abandoned slice (info[1]) and what state the engine is in (engine.hip: take_status, sync_and_check).
+        const bool latched = info && (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & DQ_STATUS_CENSUS);
         if (wave == 0) {
             unsigned spins = 0; bool all_in = false;
             for (;;) {
@@ -556,7 +556,7 @@ __global__ __launch_bounds__(256) void slice_sm_kernel(UpdateDesc d, SliceSync* 
             if (!all_in && lane == 0) {
                 __hip_atomic_store(&sy->seq, ((unsigned long long)slice_tag(epoch, 1) << 32) | SLICE_SOLO_BIT | SLICE_FINAL_BIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_fetch_add(&sy->solo_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (info) { atomicOr(info, 8); atomicCAS(info + 1, 0, l + 1); }      // info[1]: first abandoned slice + 1
+                if (info) { atomicOr(info, DQ_STATUS_CENSUS); atomicCAS(info + 1, 0, l + 1); }      // info[1]: first abandoned slice + 1
                 d.acc_out[(long)chain * d.acc_stride + acc_slot] = 0;               // nothing was proposed in this slice
             }
         }
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(256) void slice_sm_kernel(UpdateDesc d, SliceSync* 
                     if (++spins > SM_SPIN_LIMIT) { broken = true; break; }
                     __builtin_amdgcn_s_sleep(1);
                 }
-                if (broken && lane == 0) { __hip_atomic_store(&sy->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (info) atomicOr(info, 4); }
+                if (broken && lane == 0) { __hip_atomic_store(&sy->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (info) atomicOr(info, DQ_STATUS_HANDOFF); }
             }
             __syncthreads();                                          // G changed: the next window reloads the diagonal and restarts its prefetch
             SMX({ unsigned long long th1; SMT(th1) t_hand += th1 - th0; })

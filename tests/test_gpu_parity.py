@@ -541,10 +541,10 @@ def test_alternative_kernel_paths_in_subprocess(hip):
 
 
 def test_alternative_kernel_paths_above_256_in_subprocess(hip):
-    """The switches that only matter above N = 256 (split-K instead of the LDS-staged GEMM, blocked LU + substitution instead of the
-    Gauss-Jordan solve, per-column instead of blocked triangular solve, streaming instead of cooperative QRCP, kernel pairs instead of
-    the persistent sub-matrix slice kernel) at 24x24 and 20x20: same HS fields and accepted counts as the default path of this
-    process, G after initialisation and after a half sweep to 1e-9 of its largest entry (other summation orders)."""
+    """The switches above N = 256 (blocked LU + substitution instead of the Gauss-Jordan solve, streaming QRCP and the column-pivoted
+    kernels instead of the panel-pivoted QR, kernel pairs instead of the persistent sub-matrix slice kernel) at 24x24 and 20x20: same
+    HS fields and accepted counts as the default path of this process, G after initialisation and after a half sweep to 1e-9 of its
+    largest entry (other summation orders)."""
     import subprocess, sys, json, tempfile
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     def body(L):
@@ -557,7 +557,7 @@ def test_alternative_kernel_paths_above_256_in_subprocess(hip):
             "    e = m.engine(dqmc_amd.lib()); e.set_fields(f); e.init(); G0 = e.get_G(); e.sweep_0_to_beta(*st)\n"
             "    np.savez(sys.argv[1] + str(L) + '.npz', G0=G0, G1=e.get_G(), f=e.get_fields(), acc=e.stats().n_accepted)\n") % root
     ref = {L: body(L) for L in (24, 20)}
-    for env in ({"DQMC_GJ_MAX_N": "256"}, {"DQMC_QR_STREAMING": "1"}, {"DQMC_QR_PANEL": "0"}, {"DQMC_SLICE_MULTIKERNEL": "1"}):
+    for env in ({"DQMC_LU_CLASSIC": "1"}, {"DQMC_QR_STREAMING": "1"}, {"DQMC_QR_PANEL": "0"}, {"DQMC_SLICE_MULTIKERNEL": "1"}):
         with tempfile.TemporaryDirectory() as td:
             e2 = dict(os.environ); e2.update(env)
             out = subprocess.run([sys.executable, "-c", code, os.path.join(td, "r")], env=e2, capture_output=True, text=True, timeout=600)
