@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "sweep_unequal_time", "get_G_tau", "half_warp", "measure_unequal_time", "measure_unequal_fetch",
     "comm_unique_id", "comm_create_rccl", "comm_create_callbacks", "comm_destroy", "comm_rank", "comm_world_size",
     "comm_transport", "comm_barrier", "comm_allreduce_sum", "comm_selftest", "partner_rank", "replica_exchange_round",
+    "replica_exchange_batch",
 ]
 
 UNIQUE_ID_BYTES = 128
@@ -137,6 +138,8 @@ class DqmcLib:
             g("comm_allreduce_sum").argtypes = [C.c_void_p, c_double_p, C.c_int]
             g("partner_rank").argtypes = [C.c_int, C.c_int, C.c_int]
             g("replica_exchange_round").argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(ExchangeResult)]
+        if self.has_symbol("replica_exchange_batch"):
+            g("replica_exchange_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_int, c_double_p, C.POINTER(ExchangeResult)]
         g("to_ldr").argtypes = [C.c_int] + [c_double_p] * 4
         g("ldr_mul_mat").argtypes = [C.c_int] + [c_double_p] * 7
         g("mat_mul_ldr").argtypes = [C.c_int] + [c_double_p] * 7
@@ -218,6 +221,17 @@ class DqmcLib:
     def partner_rank(self, rank: int, world: int, attempt: int) -> int:
         return int(self._sym("partner_rank")(rank, world, attempt))
 
+    def exchange_batch(self, engine: "Engine", attempt: int, u, comm: Optional["Comm"] = None) -> list:
+        """dqmc_replica_exchange_batch: one round for every chain of `engine` (chain c = replica rank*C + c; comm None: the
+        engine's chains are the whole world).  u: shape (C,), read only where a chain decides.  Returns C ExchangeResult, partner =
+        global replica index."""
+        uv = np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(-1))
+        if uv.shape != (engine.C,):
+            raise ValueError(f"u must have shape ({engine.C},), got {uv.shape}")
+        res = (ExchangeResult * engine.C)()
+        self.check(self._sym("replica_exchange_batch")(engine._h, comm._h if comm is not None else None, int(attempt), _p(uv), res))
+        return list(res)
+
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(UNIQUE_ID_BYTES)
         self.check(self._sym("comm_unique_id")(buf))
@@ -280,6 +294,10 @@ class Comm:
         res = ExchangeResult()
         self.lib.check(self.lib._sym("replica_exchange_round")(engine._h, self._h, int(attempt), float(u), C.byref(res)))
         return res
+
+    def exchange_batch(self, engine: "Engine", attempt: int, u) -> list:
+        """dqmc_replica_exchange_batch over this communicator: chain c of `engine` is replica rank*C + c."""
+        return self.lib.exchange_batch(engine, attempt, u, comm=self)
 
     def close(self):
         if self._h is not None:

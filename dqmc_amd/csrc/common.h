@@ -246,10 +246,12 @@ int qr_init_device();
 int qr_colown_init_device();
 int init_device_kernels(int device);
 
-// ---- engine.hip internals replica.hip needs: the HBM-resident HS fields of a single-chain engine ----
+// ---- engine.hip internals replica.hip needs: the HBM-resident HS fields [C][nt][n] of an engine ----
 struct EngineFieldsView { int device, n, nt, n_chains; int8_t* fields; hipStream_t stream; };
 int engine_fields_view(dqmc_engine* h, EngineFieldsView* v);
 // the device fields were overwritten in place: rebuild the exp(+-g eta) tables, the stack and G are stale until dqmc_init
 int engine_fields_changed(dqmc_engine* h);
+// the engine's replica-exchange scratch, allocated on first use: saved [C][nt][n] int8, recv [2][nt][n] int8, tab [2][C] int
+int engine_exchange_scratch(dqmc_engine* h, int8_t** saved, int8_t** recv, int** tab);
 
 }  // namespace dq

@@ -347,6 +347,7 @@ struct Engine {
     int slice_late_tile = -1, slice_late_us = 0;                 // DQMC_DEBUG_SLICE_LATE=<tile>:<us>: that flush workgroup checks in only after <us> microseconds (test of a LATE arrival)
     int slice_absent_tile = -1;                                  // DQMC_DEBUG_SLICE_ABSENT=<tile>, read when the engine is created: that flush workgroup never checks in (test of the solo fall-back)
     int* acc = nullptr;                                          // [C][nt]
+    int8_t* xsaved = nullptr; int8_t* xrecv = nullptr; int* xtab = nullptr;   // replica exchange (replica.hip): own fields [C][nt][n], two received configurations, [2][C] ints
     double* err = nullptr;                                       // [C][n_stack]
     DevStats* dstats = nullptr;                                  // [C]
     double* r1scratch = nullptr;
@@ -373,7 +374,7 @@ struct Engine {
         for (auto& p : ev_pairs) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
         if (stage_free) (void)hipEventDestroy(stage_free);
         void* ptrs[] = {expKh, invexpKh, hwOut, utMeasNow, utMeasSum, utG[0], utG[1], utG[2], utTmp, utErr, utL[0], utL[1], utD[0], utD[1], utR[0], utR[1], utP[0], utP[1], meas_now, meas_sum, GT, slice_sync, prep, stackP, expK, invexpK, cb_partner, cb_par, fields, expv, invexpv, tabs, tab8, G, pg_eye, pg_ones, Gtmp, bb0, bb1, stackL, stackD, stackR, tmpL, tmpD, tmpR,
-                        logdet, rs_perm, rs_k, rs_u, Upanel, Wpanel, Cpanel, ibuf, ijp, state, acc, err, dstats, r1scratch};
+                        logdet, rs_perm, rs_k, rs_u, Upanel, Wpanel, Cpanel, ibuf, ijp, state, acc, err, dstats, r1scratch, xsaved, xrecv, xtab};
         for (void* p : ptrs) if (p) (void)hipFree(p);
         if (h_stage) (void)hipHostFree(h_stage);
     }
@@ -832,6 +833,15 @@ int engine_fields_changed(dqmc_engine* h) {
     Engine& e = h->e;
     e.stack_valid = false; e.gt_valid = false;
     return launch_build_expv(e.fields, (long)e.nt * e.n, e.nt, e.n, e.tab8, e.expv, e.invexpv, (long)e.nt * e.n, e.C, e.s);
+}
+int engine_exchange_scratch(dqmc_engine* h, int8_t** saved, int8_t** recv, int** tab) {
+    if (!h) { set_error("null engine"); return DQMC_EINVAL; }
+    Engine& e = h->e;
+    if (!e.xsaved) {
+        DQ_TRY(e.dalloc(&e.xsaved, (size_t)e.C * e.nt * e.n)); DQ_TRY(e.dalloc(&e.xrecv, (size_t)2 * e.nt * e.n)); DQ_TRY(e.dalloc(&e.xtab, (size_t)2 * e.C));
+    }
+    *saved = e.xsaved; *recv = e.xrecv; *tab = e.xtab;
+    return 0;
 }
 }  // namespace dq
 

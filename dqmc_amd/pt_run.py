@@ -8,7 +8,13 @@ over an RCCL communicator (include/dqmc_hip.h), the field arrays going HBM to HB
 
 torch.distributed only carries the rendezvous (the 128-byte RCCL id) here.  The number of betas must equal the world
 size and the world size must be even, the checks the reference makes before MPI_Abort (source/main.cpp:52-63).  The C++
-driver (dqmc_amd/host/main.cpp) is the same loop without Python."""
+driver (dqmc_amd/host/main.cpp) is the same loop without Python.
+
+--replicas-per-gpu K > 1: every rank holds ONE batched engine with K consecutive betas (replica rank*K + c in chain c), the
+world has world_size * K replicas and dqmc_replica_exchange_batch runs the rounds -- pairs inside an engine swap on the
+device, chain 0 / chain K-1 pair with the neighbour ranks over the communicator.  On one process no communicator is needed:
+
+    python dqmc_amd/pt_run.py --replicas-per-gpu 8 --sweeps 40 --sweep-steps 5"""
 from __future__ import annotations
 
 import argparse
@@ -90,6 +96,83 @@ def run_pt(d, lib, betas, L, U, nt, n_stab, therm, sweeps, sweep_steps, seed=123
     return sweeps / dt, attempt, accepted
 
 
+def run_pt_batched(d, lib, betas, K, L, U, nt, n_stab, therm, sweeps, sweep_steps, seed=1234, log=print, transport="rccl", device=None):
+    """run_pt with K replicas per rank in one batched engine: replica g = rank*K + c has betas[g], its own fields and generator
+    (seeded as run_pt seeds rank g).  Returns (replica sweeps/s of this rank's engine over the slowest rank's time, exchange_attempt,
+    accepted swaps of replica 0)."""
+    from dqmc_amd import HubbardModel
+    W = d.world * K
+    if len(betas) != W:
+        raise SystemExit(f"ERROR: The number of betas ({len(betas)}) must match the number of replicas ({d.world} processes x {K}).")
+    if W % 2 != 0:
+        raise SystemExit(f"ERROR: the number of replicas ( {W} ) needs to be even for replica exchange")
+    dev = d.local_rank if device is None else device
+    comm = None
+    if d.world > 1:
+        import torch.distributed as dist
+        if transport == "rccl":
+            ids = [lib.comm_unique_id() if d.rank == 0 else None]
+            dist.broadcast_object_list(ids, src=0)
+            comm = lib.comm_rccl(ids[0], d.world, d.rank, dev)
+        else:
+            comm = lib.comm_callbacks(d.world, d.rank, gloo_sendrecv(dist))
+    gs = [d.rank * K + c for c in range(K)]
+    ms = [HubbardModel(L1=L, L2=L, U=U, beta=float(betas[g]), nt=nt, n_stab=n_stab) for g in gs]
+    eng = lib.engine(ms[0].n, nt, n_stab, [m.g for m in ms], ms[0].gamma, ms[0].eta, np.stack([m.expK for m in ms]),
+                     np.stack([m.invexpK for m in ms]), device=dev, n_chains=K)
+    eng.set_fields(np.stack([m.random_fields(seed + g) for m, g in zip(ms, gs)])); eng.init()
+    rngs = [np.random.default_rng(seed + 1000 + g) for g in gs]
+
+    def sweep():
+        for fn in (eng.sweep_0_to_beta, eng.sweep_beta_to_0):
+            st = [ms[c].random_stream(rngs[c]) for c in range(K)]
+            fn(*(np.stack([x[k] for x in st]) for k in range(3)))
+
+    def barrier():
+        if comm is not None:
+            comm.barrier()
+
+    for _ in range(therm):
+        sweep()
+    eng.sync(); barrier()
+    attempt = accepted = 0
+    t_ex = 0.0
+    t0 = time.perf_counter()
+    for isweep in range(1, sweeps + 1):
+        if isweep % sweep_steps == 0:
+            barrier()
+            attempt += 1
+            u = np.zeros(K)
+            for c, g in enumerate(gs):                                 # only deciders draw (source/update.cpp:96)
+                if g < lib.partner_rank(g, W, attempt):
+                    u[c] = rngs[c].random()
+            te = time.perf_counter()
+            res = lib.exchange_batch(eng, attempt, u, comm=comm)
+            t_ex += time.perf_counter() - te
+            if d.rank == 0:
+                accepted += res[0].accepted
+        sweep()
+    eng.sync(); barrier()
+    dt = time.perf_counter() - t0
+    st = eng.stats()
+    acc = float(np.mean([s.n_accepted / max(1, s.n_proposed) for s in st]))
+    sums = comm.allreduce_sum([dt, acc]) if comm is not None else np.array([dt, acc])
+    if d.world > 1:
+        import torch.distributed as dist
+        slow = [None] * d.world
+        dist.all_gather_object(slow, dt)
+        dt = max(slow)
+    if d.rank == 0:
+        log(f"PT: {W} replicas = {d.world} rank(s) x {K} chains over {comm.transport if comm is not None else 'one engine'}, {sweeps} sweeps in "
+            f"{dt:.2f} s = {W * sweeps / dt:.2f} replica sweeps/s total; acceptance {sums[1] / d.world:.4f}; exchange rate of replica 0 "
+            f"{accepted / max(1, attempt):.4f} ({accepted}/{attempt}), {1e3 * t_ex / max(1, attempt):.1f} ms per round; "
+            f"max wrap err {max(s.max_err for s in st):.3e}")
+    if comm is not None:
+        comm.close()
+    eng.close()
+    return K * sweeps / dt, attempt, accepted
+
+
 def main():
     from dqmc_amd import CFG4_BETAS, CONFIGS
     cfg = CONFIGS["cfg4"]
@@ -102,12 +185,18 @@ def main():
     ap.add_argument("--therm", type=int, default=5)
     ap.add_argument("--sweeps", type=int, default=20)
     ap.add_argument("--sweep-steps", type=int, default=5)
+    ap.add_argument("--replicas-per-gpu", type=int, default=1,
+                    help="betas per rank, held as the chains of one batched engine (1: one single-chain engine per rank)")
     args = ap.parse_args()
     import dqmc_amd
     from dqmc_amd.launch import dist_init, finalize
     d = dist_init()
     betas = [float(b) for b in args.betas.split(",") if b.strip()]
-    run_pt(d, dqmc_amd.lib(), betas, args.L, args.U, args.nt, args.n_stab, args.therm, args.sweeps, args.sweep_steps)
+    if args.replicas_per_gpu > 1:
+        run_pt_batched(d, dqmc_amd.lib(), betas, args.replicas_per_gpu, args.L, args.U, args.nt, args.n_stab, args.therm, args.sweeps,
+                       args.sweep_steps)
+    else:
+        run_pt(d, dqmc_amd.lib(), betas, args.L, args.U, args.nt, args.n_stab, args.therm, args.sweeps, args.sweep_steps)
     finalize(d)
 
 

@@ -331,6 +331,32 @@ typedef struct dqmc_exchange_result {
 int dqmc_replica_exchange_round(dqmc_engine* e, dqmc_comm* comm, int exchange_attempt, double u,
                                 dqmc_exchange_result* result);
 
+/* The same round for every chain of a batched engine (dqmc_create_batch): chain c of rank
+ * dqmc_comm_rank(comm) is replica rank*C + c of a world of W = ranks * C (comm NULL: the
+ * engine's C chains are the whole world), with chain c at its own beta.  Partners are
+ * dqmc_partner_rank(replica, W, exchange_attempt); the lower replica index of a pair decides
+ * with u[c] < min(1, exp(-deltaS)).  u: [C], read only where chain c decides (the caller draws
+ * only for those, as only the reference's deciding ranks advance their generator).
+ * result: [C]; partner is the GLOBAL replica index, -1 for none.  In-engine pairs swap on the
+ * device and share one batched dqmc_init (a second one runs only when some pair was
+ * rejected); a pair that crosses to a neighbour rank (chain 0 / chain C-1) runs the protocol
+ * of dqmc_replica_exchange_round over comm.  What moves is the field configuration; the
+ * chain keeps its beta, dqmc_stats, the measurement bins, the checkerboard parameters and its
+ * CU reservation.  On return G, the stack and log det of every chain belong to the fields it
+ * now holds; the unequal-time series of the last dqmc_sweep_unequal_time is stale, as after
+ * dqmc_init.  A local failure rejects every pair of the engine (own fields restored and
+ * re-initialised), is reported to the boundary partners and returned.  DQMC_EINVAL with the
+ * fields untouched for: W odd (source/main.cpp:58-62), C = 1 without comm, a null pointer, an
+ * RCCL communicator on another device.  With a communicator of more than one rank the call is
+ * collective: every rank calls it for the same attempt, and before anything moves one
+ * dqmc_comm_allreduce_sum settles that all ranks hold the same C and nt*n_sites and accepted
+ * their arguments; otherwise EVERY rank returns DQMC_EINVAL with its fields untouched.  The
+ * single-chain dqmc_replica_exchange_round is the C = 1 case of the same round without that
+ * all-reduce (its messages are unchanged); the ranks of one world use one entry point or the
+ * other.  Synchronous.                                                                       */
+int dqmc_replica_exchange_batch(dqmc_engine* e, dqmc_comm* comm, int exchange_attempt, const double* u,
+                                dqmc_exchange_result* result);
+
 /* Number of accepted proposals / kernel time (ms, HIP events on the engine's
  * stream) spent inside the local-update kernels since the last call -- the
  * live measurement bench.py uses for the rank-1 roofline.                    */
