@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <memory>
 #include <string>
 
 struct dqmc_engine;
@@ -30,11 +31,24 @@ const char* get_error();
         }                                                                               \
     } while (0)
 
-#define DQ_TRY_RC(expr)             \
+#define DQ_TRY(expr)                \
     do {                            \
         int _rc = (expr);           \
         if (_rc != 0) return _rc;   \
     } while (0)
+
+// ---- device memory: one owner per buffer ------------------------------------------
+// DevPtr<T> frees its device array when it goes, PinnedPtr its pinned host buffer.  dev_alloc is the only place device memory is
+// allocated: DQMC_ENODEVICE (with `out` unchanged) when hipMalloc fails.
+template <class T, hipError_t (*Free)(void*)> struct HipDelete { void operator()(T* p) const { (void)Free(p); } };
+template <class T> using DevPtr = std::unique_ptr<T[], HipDelete<T, hipFree>>;
+using PinnedPtr = std::unique_ptr<char[], HipDelete<char, hipHostFree>>;
+template <class T> int dev_alloc(DevPtr<T>& out, size_t count) {
+    void* p = nullptr;
+    DQ_HIP(hipMalloc(&p, sizeof(T) * count));
+    out.reset(static_cast<T*>(p));
+    return 0;
+}
 
 // ---- device status block ----------------------------------------------------
 // 4 ints per context (Ctx::info, engine.hip), zeroed at creation, read and cleared by the host after a sync (take_status, engine.hip).

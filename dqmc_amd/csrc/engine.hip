@@ -24,12 +24,6 @@ static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 const char* get_error() { return g_err.c_str(); }
 
-#define DQ_TRY(expr)            \
-    do {                        \
-        int _rc = (expr);       \
-        if (_rc != 0) return _rc; \
-    } while (0)
-
 // hipFuncSetAttribute is per device: every device an engine (or the stateless context) lives on gets the attributes once
 int init_device_kernels(int device) {
     static std::mutex mu; static bool done[64] = {};
@@ -110,63 +104,67 @@ struct LdrRef {                 // a batched LDR triple in HBM
     int* jpvt = nullptr;        // [C][n] pivot order storage of this triple (may be null)
     bool* tri = nullptr;        // host flag: R is the permuted-triangular factor of ONE to_LDR (jpvt valid)
 };
+// k batched LDR triples: L, R [k][C][nn], d and the pivot order of R [k][C][n], and the host flag `tri` of each triple
+struct LdrStore {
+    int n = 0, C = 0;
+    DevPtr<double> L, d, R;
+    DevPtr<int> jpvt;
+    std::unique_ptr<bool[]> tri;               // an array on the heap: LdrRef::tri stays valid when the store is moved
+    int alloc(int k, int n_, int C_) {
+        n = n_; C = C_;
+        const size_t nn = (size_t)n * n;
+        DQ_TRY(dev_alloc(L, (size_t)k * C * nn)); DQ_TRY(dev_alloc(d, (size_t)k * C * n));
+        DQ_TRY(dev_alloc(R, (size_t)k * C * nn)); DQ_TRY(dev_alloc(jpvt, (size_t)k * C * n));
+        tri.reset(new bool[k]());
+        return 0;
+    }
+    LdrRef at(int i) const {
+        const long nn = (long)n * n;
+        return LdrRef{Mat{L.get() + (long)i * C * nn, nn}, Vec{d.get() + (long)i * C * n, (long)n}, Mat{R.get() + (long)i * C * nn, nn},
+                      jpvt.get() + (long)i * C * n, &tri[i]};
+    }
+};
 
 struct Ctx {
     int n = 0, C = 0, device = 0;
     long nn = 0;
     hipStream_t stream = nullptr;
-    static constexpr int NT = 10;              // workspace matrices
-    double* pool = nullptr;                    // NT * C * nn
-    double* vpool = nullptr;                   // vectors: 8 * C * n
-    int* ipool = nullptr;                      // 3 * C * n ints + info
-    double* spool = nullptr;                   // scalars: 4 * C
-    unsigned long long* qsync = nullptr;       // cooperative QRCP records
-    int* qabort = nullptr;                     // cooperative QRCP abort words: C
-    double* tinv = nullptr;                    // Gauss-Jordan panel inverses: 2048 * C
-    double* qpw = nullptr;                     // panel-pivoted QR (qr_panel.hip): qr_panel_work_doubles(n) * C
-    int* qpivpos = nullptr;                    // ... and its pivot positions: n * C
-    double* trinv = nullptr;                   // blocked triangular solve: inverses of the 16 x 16 diagonal blocks, 16 * (n + 16) * C
+    static constexpr int NT = 6, NV = 5;       // matrices T0 .. T4 and the Gauss-Jordan scratch T5; vectors V0 .. V3 and the QR tau V4
+    DevPtr<double> pool;                       // NT * C * nn
+    DevPtr<double> vpool;                      // NV * C * n
+    DevPtr<int> ipool;                         // 3 * C * n ints + info
+    DevPtr<unsigned long long> qsync;          // cooperative QRCP records
+    DevPtr<int> qabort;                        // cooperative QRCP abort words: C
+    DevPtr<double> tinv;                       // Gauss-Jordan panel inverses: 2048 * C
+    DevPtr<double> qpw;                        // panel-pivoted QR (qr_panel.hip): qr_panel_work_doubles(n) * C
+    DevPtr<int> qpivpos;                       // ... and its pivot positions: n * C
+    DevPtr<double> trinv;                      // blocked triangular solve: inverses of the 16 x 16 diagonal blocks, 16 * (n + 16) * C
     KernelPlan plan{};                         // the kernel families of this (n, C); each family's workspace above exists only when chosen
 
-    Mat T(int k) const { return Mat{pool + (long)k * C * nn, nn}; }
-    Vec V(int k) const { return Vec{vpool + (long)k * C * n, (long)n}; }
-    int* jpvt() const { return ipool; }
-    int* lperm() const { return ipool + (long)C * n; }
-    int* rowpos() const { return ipool + 2L * C * n; }
-    int* info() const { return ipool + 3L * C * n; }
-    double* logsum() const { return spool; }           // C
-    double* scal(int k) const { return spool + (long)k * C; }
+    Mat T(int k) const { return Mat{pool.get() + (long)k * C * nn, nn}; }
+    Vec V(int k) const { return Vec{vpool.get() + (long)k * C * n, (long)n}; }
+    int* jpvt() const { return ipool.get(); }
+    int* lperm() const { return ipool.get() + (long)C * n; }
+    int* rowpos() const { return ipool.get() + 2L * C * n; }
+    int* info() const { return ipool.get() + 3L * C * n; }
 
     int init(int n_, int C_, int device_) {
         n = n_; C = C_; device = device_; nn = (long)n * n;
         DQ_HIP(hipSetDevice(device));
         DQ_TRY(init_device_kernels(device));
         DQ_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        DQ_HIP(hipMalloc(&pool, sizeof(double) * NT * C * nn));
-        DQ_HIP(hipMalloc(&vpool, sizeof(double) * 8 * C * n));
-        DQ_HIP(hipMalloc(&ipool, sizeof(int) * (3L * C * n + 4)));
-        DQ_HIP(hipMalloc(&spool, sizeof(double) * 4 * C));
+        DQ_TRY(dev_alloc(pool, (size_t)NT * C * nn));
+        DQ_TRY(dev_alloc(vpool, (size_t)NV * C * n));
+        DQ_TRY(dev_alloc(ipool, 3L * C * n + 4));
         plan = KernelPlan::pick(n, C);
-        if (plan.qr == QrFamily::Cooperative) { DQ_HIP(hipMalloc(&qsync, sizeof(unsigned long long) * qrcp_coop_sync_granules(n) * C)); DQ_HIP(hipMalloc(&qabort, sizeof(int) * C)); }
-        if (plan.qr == QrFamily::Panel) { DQ_HIP(hipMalloc(&qpw, sizeof(double) * qr_panel_work_doubles(n) * C)); DQ_HIP(hipMalloc(&qpivpos, sizeof(int) * (size_t)n * C)); }
-        if (plan.solve == KernelPlan::Solve::GaussJordan) DQ_HIP(hipMalloc(&tinv, sizeof(double) * 2048 * C));
-        if (plan.rinv == KernelPlan::Rinv::Blocked) DQ_HIP(hipMalloc(&trinv, sizeof(double) * 16 * (n + 16) * C));
-        DQ_HIP(hipMemsetAsync(ipool, 0, sizeof(int) * (3L * C * n + 4), stream));
+        if (plan.qr == QrFamily::Cooperative) { DQ_TRY(dev_alloc(qsync, (size_t)qrcp_coop_sync_granules(n) * C)); DQ_TRY(dev_alloc(qabort, C)); }
+        if (plan.qr == QrFamily::Panel) { DQ_TRY(dev_alloc(qpw, (size_t)qr_panel_work_doubles(n) * C)); DQ_TRY(dev_alloc(qpivpos, (size_t)n * C)); }
+        if (plan.solve == KernelPlan::Solve::GaussJordan) DQ_TRY(dev_alloc(tinv, (size_t)2048 * C));
+        if (plan.rinv == KernelPlan::Rinv::Blocked) DQ_TRY(dev_alloc(trinv, (size_t)16 * (n + 16) * C));
+        DQ_HIP(hipMemsetAsync(ipool.get(), 0, sizeof(int) * (3L * C * n + 4), stream));
         return 0;
     }
-    ~Ctx() {
-        if (pool) (void)hipFree(pool);
-        if (vpool) (void)hipFree(vpool);
-        if (ipool) (void)hipFree(ipool);
-        if (spool) (void)hipFree(spool);
-        if (qsync) (void)hipFree(qsync);
-        if (qabort) (void)hipFree(qabort);
-        if (tinv) (void)hipFree(tinv);
-        if (trinv) (void)hipFree(trinv);
-        if (qpw) (void)hipFree(qpw);
-        if (qpivpos) (void)hipFree(qpivpos);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~Ctx() { if (stream) (void)hipStreamDestroy(stream); }
 
     int gemm(CMat A, CMat B, Mat Cm, CVec rs = CVec(), CVec ks = CVec(), CVec cs = CVec(), int transA = 0, int accumulate = 0, Mat CT = Mat{nullptr, 0}) {
         GemmDesc g; g.A = A; g.B = B; g.C = Cm; g.CT = CT; g.rs = rs; g.ks = ks; g.cs = cs; g.n = n; g.transA = transA; g.accumulate = accumulate;
@@ -177,16 +175,16 @@ struct Ctx {
     // triangular fast path later; its pivot order is written straight into out.jpvt.
     int to_ldr(Mat A, LdrRef out, bool direct = true) {
         const bool keep = direct && out.jpvt != nullptr;
-        QrWork w{V(7).p, (long)n, keep ? out.jpvt : jpvt(), (long)n};
-        w.sync = qsync; w.sync_stride = qrcp_coop_sync_granules(n); w.abort_words = qabort; w.info = info();
-        w.pw = qpw; w.pw_stride = qr_panel_work_doubles(n); w.pivpos = qpivpos; w.pivpos_stride = n;
+        QrWork w{V(4).p, (long)n, keep ? out.jpvt : jpvt(), (long)n};
+        w.sync = qsync.get(); w.sync_stride = qrcp_coop_sync_granules(n); w.abort_words = qabort.get(); w.info = info();
+        w.pw = qpw.get(); w.pw_stride = qr_panel_work_doubles(n); w.pivpos = qpivpos.get(); w.pivpos_stride = n;
         if (out.tri) *out.tri = keep;
         return launch_to_ldr(plan.qr, A, out.L, out.d, out.R, w, n, C, stream);
     }
     // X = F.R^-1 diag(dinv): permuted triangular solve when F.R is a single QR factor, LU otherwise
     int r_inverse_scaled(LdrRef F, CVec dinv, Mat X, Mat lu_scratch) {
         if (F.tri && *F.tri && F.jpvt) {
-            if (plan.rinv == KernelPlan::Rinv::Blocked) return launch_tri_solve(F.R, F.jpvt, n, X, dinv, trinv, 16L * (n + 16), n, C, stream);
+            if (plan.rinv == KernelPlan::Rinv::Blocked) return launch_tri_solve(F.R, F.jpvt, n, X, dinv, trinv.get(), 16L * (n + 16), n, C, stream);
             return launch_lu_solve(F.R, F.jpvt, n, X, dinv, 2, n, C, stream);
         }
         DQ_TRY(launch_copy(F.R, lu_scratch, nn, C, stream));
@@ -218,10 +216,10 @@ struct Ctx {
         return gemm(T(2), F2.R, out.R);
     }
     // Y = M^-1 RHS (arma::solve): blocked Gauss-Jordan (result in `out`) or dgetrf + dgetrs (result overwrites RHS), as the plan says.
-    // Returns the matrix holding Y in *Y.  M and RHS are destroyed.  (uses T9 as scratch)
+    // Returns the matrix holding Y in *Y.  M and RHS are destroyed.  (uses T5 as scratch)
     int solve(Mat M, Mat RHS, Mat out, double* logdet_acc, Mat* Y) {
         if (plan.solve == KernelPlan::Solve::GaussJordan) {
-            DQ_TRY(launch_gj_solve(M, RHS, out, T(9), tinv, lperm(), n, rowpos(), n, logdet_acc, 1, info(), n, C, stream));
+            DQ_TRY(launch_gj_solve(M, RHS, out, T(5), tinv.get(), lperm(), n, rowpos(), n, logdet_acc, 1, info(), n, C, stream));
             *Y = out; return 0;
         }
         DQ_TRY(launch_lu_blocked(M, lperm(), n, rowpos(), n, logdet_acc, 1, info(), n, C, stream));
@@ -301,56 +299,53 @@ struct Engine {
     long nn = 0;
     std::vector<int> loc_l_end;
     std::vector<double> g_host, gamma_host, eta_host;
-    std::vector<unsigned char> seen;                             // scratch of the random-stream validation
-    Ctx ctx;
+    std::vector<unsigned char> seen;                             // scratch of check_stream
+    Ctx ctx;                                                     // owns the stream; declared before every buffer below, so it outlives them
     hipStream_t s = nullptr;
 
-    double* expK = nullptr; double* invexpK = nullptr;           // [C][nn]
-    double* expKh = nullptr; double* invexpKh = nullptr;         // [nn] each: exp(-+ dtau K / 2) of dqmc_half_warp, uploaded on first use
-    double* hwOut = nullptr;                                     // [C][nn] result of dqmc_half_warp
+    DevPtr<double> expK, invexpK;                                // [C][nn]
     // checkerboard break-up of exp(-+dtau K) (dqmc_set_checkerboard): wraps and B-bar products apply the pair factors directly
     bool cb = false; int cb_groups = 0;
-    int* cb_partner = nullptr;                                   // [cb_groups][n]
-    double* cb_par = nullptr;                                    // [C][4] cosh, sinh, f, 1/f
-    int8_t* fields = nullptr;                                    // [C][nt][n]
-    double* expv = nullptr; double* invexpv = nullptr;           // [C][nt][n]
-    UpdateTables* tabs = nullptr; double* tab8 = nullptr;        // [C], [C][8]
+    DevPtr<int> cb_partner;                                      // [cb_groups][n]
+    DevPtr<double> cb_par;                                       // [C][4] cosh, sinh, f, 1/f
+    DevPtr<int8_t> fields;                                       // [C][nt][n]
+    DevPtr<double> expv, invexpv;                                // [C][nt][n]
+    DevPtr<UpdateTables> tabs; DevPtr<double> tab8;              // [C], [C][8]
     bool gt_valid = false;                                       // GT == G^T right now (set by the wraps, cleared by everything else that writes G)
-    double* G = nullptr; double* Gtmp = nullptr; double* GT = nullptr;   // [C][nn]; GT: transposed copy for the local-update walk
-    double* pg_eye = nullptr; double* pg_ones = nullptr;         // identity [nn] and ones [n]: operands of the first piggybacked B-bar factor of a block (single chain)
-    double* bb0 = nullptr; double* bb1 = nullptr;                // Bbar ping-pong
-    double* stackL = nullptr; double* stackD = nullptr; double* stackR = nullptr;
-    double* tmpL = nullptr; double* tmpD = nullptr; double* tmpR = nullptr;   // one spare LDR (init_stacks)
-    int* stackP = nullptr;                                       // [n_stack][C][n] pivot order of each entry's R
-    std::unique_ptr<bool[]> stack_tri;                           // [n_stack] R is a single permuted-triangular factor
-    double* logdet = nullptr;                                    // [C]
-    int32_t* rs_perm = nullptr; uint8_t* rs_k = nullptr; double* rs_u = nullptr;   // [C][nt][n]
-    void* h_stage = nullptr; size_t h_stage_bytes = 0;           // pinned staging for the random stream
+    DevPtr<double> G, Gtmp, GT;                                  // [C][nn]; GT: transposed copy for the local-update walk
+    DevPtr<double> pg_eye, pg_ones;                              // identity [nn] and ones [n]: operands of the first piggybacked B-bar factor of a block (single chain)
+    DevPtr<double> bb0, bb1;                                     // Bbar ping-pong
+    LdrStore stack;                                              // n_stack triples
+    LdrStore spare;                                              // one spare triple (init)
+    DevPtr<double> logdet;                                       // [C]
+    DevPtr<int32_t> rs_perm; DevPtr<uint8_t> rs_k; DevPtr<double> rs_u;   // [C][nt][n]
+    PinnedPtr h_stage;                                           // pinned staging for the random stream
     hipEvent_t stage_free = nullptr;
-    double* Upanel = nullptr; double* Wpanel = nullptr;          // [C][KD][n]
-    double* Cpanel = nullptr;                                    // [C][KD][KD]
-    double* ibuf = nullptr; int* ijp = nullptr;                  // batched initialisation (init_batched): Bbar ping-pong, L, R, d, tau / pivots of every block
-    int* state = nullptr;                                        // [C][4]
-    double* prep = nullptr;                                      // [C][4n]
-    double* meas_now = nullptr; double* meas_sum = nullptr;      // [C][3 + n] equal-time observables: last evaluation / bin sums
-    // unequal-time path (allocated by the first sweep_unequal): Gtt / Gt0 / G0t [nt + 1][C][nn], B(tau,0) ping-pong LDRs, scratch
-    double* utG[3] = {nullptr, nullptr, nullptr}; double* utTmp = nullptr; double* utErr = nullptr;
-    double* utL[2] = {nullptr, nullptr}; double* utD[2] = {nullptr, nullptr}; double* utR[2] = {nullptr, nullptr}; int* utP[2] = {nullptr, nullptr};
-    bool utTri[2] = {false, false}; bool ut_valid = false;
-    double* utMeasNow = nullptr; double* utMeasSum = nullptr; long long ut_meas_count = 0;     // [C][3][nt + 1][n] dynamical observables: last / bin sums
+    DevPtr<double> Upanel, Wpanel;                               // [C][KD][n]
+    DevPtr<double> Cpanel;                                       // [C][KD][KD]
+    // The groups below are allocated on first use into a local group, which replaces the engine's only once all of it is allocated.
+    // batched initialisation (init_batched): Bbar ping-pong [2][S][nn], tau [S][n] and the to_LDR of every block (S triples)
+    struct InitBatch { DevPtr<double> bb, tau; LdrStore f; } ib;
+    DevPtr<int> state;                                           // [C][4]
+    DevPtr<double> prep;                                         // [C][4n]
+    DevPtr<double> meas_now, meas_sum;                           // [C][3 + n] equal-time observables: last evaluation / bin sums
+    // unequal-time path (sweep_unequal): Gtt / Gt0 / G0t [nt + 1][C][nn], the three before a stabilisation [3][C][nn], their errors
+    // [C][3 n_stack], dynamical observables [C][3][nt + 1][n] (last / bin sums), B(tau, 0) ping-pong (2 triples)
+    struct UnequalTime { DevPtr<double> G[3], tmp, err, meas_now, meas_sum; LdrStore bt; } ut;
+    bool ut_valid = false; long long ut_meas_count = 0;
+    struct HalfWarp { DevPtr<double> expK, invexpK, out; } hw;   // dqmc_half_warp: exp(-+ dtau K / 2) [nn] each, its result [C][nn]
     long long meas_count = 0;                                    // measurements accumulated in meas_sum
-    char* slice_sync = nullptr;                                  // [C][SLICE_SYNC_BYTES = 2 KiB] hand-off words of the persistent slice kernels (SliceSync, common.h)
+    DevPtr<char> slice_sync;                                     // [C][SLICE_SYNC_BYTES = 2 KiB] hand-off words of the persistent slice kernels (SliceSync, common.h)
     bool reserved = false;                                       // holds a CU reservation for the single-launch slice kernels (slice_reserve)
     SlicePath slice_path = SlicePath::Pairs;                     // the local-update path; lowered to the unreserved choice once a persistent kernel fails (sync_and_check)
     unsigned slice_epoch = 0;                                    // launches of the persistent slice kernel so far: the tag of its hand-off words (SliceSync, common.h)
     int slice_absent_l = -1;                                     // ...=<tile>:<slice>: only in the launch of that time slice
     int slice_late_tile = -1, slice_late_us = 0;                 // DQMC_DEBUG_SLICE_LATE=<tile>:<us>: that flush workgroup checks in only after <us> microseconds (test of a LATE arrival)
     int slice_absent_tile = -1;                                  // DQMC_DEBUG_SLICE_ABSENT=<tile>, read when the engine is created: that flush workgroup never checks in (test of the solo fall-back)
-    int* acc = nullptr;                                          // [C][nt]
-    int8_t* xsaved = nullptr; int8_t* xrecv = nullptr; int* xtab = nullptr;   // replica exchange (replica.hip): own fields [C][nt][n], two received configurations, [2][C] ints
-    double* err = nullptr;                                       // [C][n_stack]
-    DevStats* dstats = nullptr;                                  // [C]
-    double* r1scratch = nullptr;
+    DevPtr<int> acc;                                             // [C][nt]
+    struct Exchange { DevPtr<int8_t> saved, recv; DevPtr<int> tab; } xch;   // replica exchange (replica.hip): own fields [C][nt][n], two received configurations, [2][C] ints
+    DevPtr<double> err;                                          // [C][n_stack]
+    DevPtr<DevStats> dstats;                                     // [C]
     bool stack_valid = false;
     // profiling of the local-update kernels
     bool profiling = false;
@@ -358,28 +353,18 @@ struct Engine {
     size_t ev_used = 0;
     double upd_ms = 0.0; long long upd_launches = 0; long long upd_accept_base = 0;
 
-    Mat mG() const { return Mat{G, nn}; }
-    LdrRef stk(int i) const {
-        return LdrRef{Mat{stackL + (long)i * C * nn, nn}, Vec{stackD + (long)i * C * n, (long)n}, Mat{stackR + (long)i * C * nn, nn},
-                      stackP + (long)i * C * n, &stack_tri[i]};
-    }
-    CVec ev(int l) const { return CVec(expv + (long)l * n, (long)nt * n); }
-    CVec iev(int l) const { return CVec(invexpv + (long)l * n, (long)nt * n); }
+    Mat mG() const { return Mat{G.get(), nn}; }
+    CVec ev(int l) const { return CVec(expv.get() + (long)l * n, (long)nt * n); }
+    CVec iev(int l) const { return CVec(invexpv.get() + (long)l * n, (long)nt * n); }
     int stack_idx(int l) const { return l / n_stab; }            // include/dqmc.h:47
     int local_l(int l) const { return l % n_stab; }              // include/dqmc.h:48
 
-    ~Engine() {
+    ~Engine() {                                                  // the buffers are freed after the sync, the stream (ctx) after them
         if (s) (void)hipStreamSynchronize(s);
         if (reserved) slice_release(device, n, C);
         for (auto& p : ev_pairs) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
         if (stage_free) (void)hipEventDestroy(stage_free);
-        void* ptrs[] = {expKh, invexpKh, hwOut, utMeasNow, utMeasSum, utG[0], utG[1], utG[2], utTmp, utErr, utL[0], utL[1], utD[0], utD[1], utR[0], utR[1], utP[0], utP[1], meas_now, meas_sum, GT, slice_sync, prep, stackP, expK, invexpK, cb_partner, cb_par, fields, expv, invexpv, tabs, tab8, G, pg_eye, pg_ones, Gtmp, bb0, bb1, stackL, stackD, stackR, tmpL, tmpD, tmpR,
-                        logdet, rs_perm, rs_k, rs_u, Upanel, Wpanel, Cpanel, ibuf, ijp, state, acc, err, dstats, r1scratch, xsaved, xrecv, xtab};
-        for (void* p : ptrs) if (p) (void)hipFree(p);
-        if (h_stage) (void)hipHostFree(h_stage);
     }
-
-    template <class T> int dalloc(T** p, size_t count) { DQ_HIP(hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * count)); return 0; }
 
     int create(int device_, int C_, int n_, int nt_, int n_stab_, const double* g, const double* gamma, const double* eta,
                const double* eK, const double* ieK) {
@@ -393,30 +378,28 @@ struct Engine {
         slice_path = pick_slice_path(n, C, reserved);
         if (const char* a = getenv("DQMC_DEBUG_SLICE_ABSENT")) { slice_absent_tile = atoi(a); if (const char* c = strchr(a, ':')) slice_absent_l = atoi(c + 1); }
         if (const char* a = getenv("DQMC_DEBUG_SLICE_LATE")) { slice_late_tile = atoi(a); if (const char* c = strchr(a, ':')) slice_late_us = atoi(c + 1); }
-        DQ_TRY(dalloc(&expK, C * nn)); DQ_TRY(dalloc(&invexpK, C * nn));
-        DQ_TRY(dalloc(&fields, (size_t)C * nt * n)); DQ_TRY(dalloc(&expv, (size_t)C * nt * n)); DQ_TRY(dalloc(&invexpv, (size_t)C * nt * n));
-        DQ_TRY(dalloc(&tabs, C)); DQ_TRY(dalloc(&tab8, (size_t)C * 8));
-        if (C == 1) { DQ_TRY(dalloc(&pg_eye, nn)); DQ_TRY(dalloc(&pg_ones, (size_t)n)); DQ_TRY(launch_set_identity(Mat{pg_eye, nn}, n, 1, s)); const std::vector<double> one_h((size_t)n, 1.0); DQ_HIP(hipMemcpy(pg_ones, one_h.data(), sizeof(double) * n, hipMemcpyHostToDevice)); }
-        DQ_TRY(dalloc(&G, C * nn)); DQ_TRY(dalloc(&Gtmp, C * nn)); DQ_TRY(dalloc(&GT, C * nn)); DQ_TRY(dalloc(&bb0, C * nn)); DQ_TRY(dalloc(&bb1, C * nn));
-        DQ_TRY(dalloc(&stackL, (size_t)n_stack * C * nn)); DQ_TRY(dalloc(&stackD, (size_t)n_stack * C * n)); DQ_TRY(dalloc(&stackR, (size_t)n_stack * C * nn));
-        DQ_TRY(dalloc(&stackP, (size_t)n_stack * C * n)); stack_tri.reset(new bool[n_stack]());
-        DQ_TRY(dalloc(&tmpL, C * nn)); DQ_TRY(dalloc(&tmpD, (size_t)C * n)); DQ_TRY(dalloc(&tmpR, C * nn));
-        DQ_TRY(dalloc(&logdet, C));
-        DQ_TRY(dalloc(&rs_perm, (size_t)C * nt * n)); DQ_TRY(dalloc(&rs_k, (size_t)C * nt * n)); DQ_TRY(dalloc(&rs_u, (size_t)C * nt * n));
-        DQ_TRY(dalloc(&Upanel, (size_t)C * UPDATE_KD * n)); DQ_TRY(dalloc(&Wpanel, (size_t)C * UPDATE_KD * n)); DQ_TRY(dalloc(&Cpanel, (size_t)C * UPDATE_KD * UPDATE_KD));
-        DQ_TRY(dalloc(&state, (size_t)C * 4)); DQ_TRY(dalloc(&prep, (size_t)C * 4 * n)); DQ_TRY(dalloc(&meas_now, (size_t)C * (3 + n))); DQ_TRY(dalloc(&meas_sum, (size_t)C * (3 + n))); DQ_HIP(hipMemsetAsync(meas_sum, 0, sizeof(double) * C * (3 + n), s)); DQ_TRY(dalloc(&slice_sync, (size_t)C * SLICE_SYNC_BYTES)); DQ_HIP(hipMemsetAsync(slice_sync, 0, (size_t)C * SLICE_SYNC_BYTES, s)); DQ_TRY(dalloc(&acc, (size_t)C * nt)); DQ_TRY(dalloc(&err, (size_t)C * n_stack));
-        DQ_TRY(dalloc(&dstats, C)); DQ_TRY(dalloc(&r1scratch, (size_t)C * (2 * n + 1)));
-        h_stage_bytes = (size_t)C * nt * n * (sizeof(int32_t) + sizeof(uint8_t) + sizeof(double));
-        DQ_HIP(hipHostMalloc(&h_stage, h_stage_bytes, hipHostMallocDefault));
+        DQ_TRY(dev_alloc(expK, C * nn)); DQ_TRY(dev_alloc(invexpK, C * nn));
+        DQ_TRY(dev_alloc(fields, (size_t)C * nt * n)); DQ_TRY(dev_alloc(expv, (size_t)C * nt * n)); DQ_TRY(dev_alloc(invexpv, (size_t)C * nt * n));
+        DQ_TRY(dev_alloc(tabs, C)); DQ_TRY(dev_alloc(tab8, (size_t)C * 8));
+        if (C == 1) { DQ_TRY(dev_alloc(pg_eye, nn)); DQ_TRY(dev_alloc(pg_ones, (size_t)n)); DQ_TRY(launch_set_identity(Mat{pg_eye.get(), nn}, n, 1, s)); const std::vector<double> one_h((size_t)n, 1.0); DQ_HIP(hipMemcpy(pg_ones.get(), one_h.data(), sizeof(double) * n, hipMemcpyHostToDevice)); }
+        DQ_TRY(dev_alloc(G, C * nn)); DQ_TRY(dev_alloc(Gtmp, C * nn)); DQ_TRY(dev_alloc(GT, C * nn)); DQ_TRY(dev_alloc(bb0, C * nn)); DQ_TRY(dev_alloc(bb1, C * nn));
+        DQ_TRY(stack.alloc(n_stack, n, C)); DQ_TRY(spare.alloc(1, n, C));
+        DQ_TRY(dev_alloc(logdet, C));
+        DQ_TRY(dev_alloc(rs_perm, (size_t)C * nt * n)); DQ_TRY(dev_alloc(rs_k, (size_t)C * nt * n)); DQ_TRY(dev_alloc(rs_u, (size_t)C * nt * n));
+        DQ_TRY(dev_alloc(Upanel, (size_t)C * UPDATE_KD * n)); DQ_TRY(dev_alloc(Wpanel, (size_t)C * UPDATE_KD * n)); DQ_TRY(dev_alloc(Cpanel, (size_t)C * UPDATE_KD * UPDATE_KD));
+        DQ_TRY(dev_alloc(state, (size_t)C * 4)); DQ_TRY(dev_alloc(prep, (size_t)C * 4 * n)); DQ_TRY(dev_alloc(meas_now, (size_t)C * (3 + n))); DQ_TRY(dev_alloc(meas_sum, (size_t)C * (3 + n))); DQ_HIP(hipMemsetAsync(meas_sum.get(), 0, sizeof(double) * C * (3 + n), s)); DQ_TRY(dev_alloc(slice_sync, (size_t)C * SLICE_SYNC_BYTES)); DQ_HIP(hipMemsetAsync(slice_sync.get(), 0, (size_t)C * SLICE_SYNC_BYTES, s)); DQ_TRY(dev_alloc(acc, (size_t)C * nt)); DQ_TRY(dev_alloc(err, (size_t)C * n_stack));
+        DQ_TRY(dev_alloc(dstats, C));
+        void* stage = nullptr;
+        DQ_HIP(hipHostMalloc(&stage, (size_t)C * nt * n * (sizeof(int32_t) + sizeof(uint8_t) + sizeof(double)), hipHostMallocDefault)); h_stage.reset(static_cast<char*>(stage));
         DQ_HIP(hipEventCreateWithFlags(&stage_free, hipEventDisableTiming));
         DQ_HIP(hipEventRecord(stage_free, s));
-        DQ_HIP(hipMemcpyAsync(expK, eK, sizeof(double) * C * nn, hipMemcpyHostToDevice, s));
-        DQ_HIP(hipMemcpyAsync(invexpK, ieK, sizeof(double) * C * nn, hipMemcpyHostToDevice, s));
-        DQ_HIP(hipMemsetAsync(fields, 0, (size_t)C * nt * n, s));
-        DQ_HIP(hipMemsetAsync(G, 0, sizeof(double) * C * nn, s));
-        DQ_HIP(hipMemsetAsync(dstats, 0, sizeof(DevStats) * C, s));
-        DQ_HIP(hipMemsetAsync(logdet, 0, sizeof(double) * C, s));
-        DQ_HIP(hipMemsetAsync(state, 0, sizeof(int) * C * 4, s));
+        DQ_HIP(hipMemcpyAsync(expK.get(), eK, sizeof(double) * C * nn, hipMemcpyHostToDevice, s));
+        DQ_HIP(hipMemcpyAsync(invexpK.get(), ieK, sizeof(double) * C * nn, hipMemcpyHostToDevice, s));
+        DQ_HIP(hipMemsetAsync(fields.get(), 0, (size_t)C * nt * n, s));
+        DQ_HIP(hipMemsetAsync(G.get(), 0, sizeof(double) * C * nn, s));
+        DQ_HIP(hipMemsetAsync(dstats.get(), 0, sizeof(DevStats) * C, s));
+        DQ_HIP(hipMemsetAsync(logdet.get(), 0, sizeof(double) * C, s));
+        DQ_HIP(hipMemsetAsync(state.get(), 0, sizeof(int) * C * 4, s));
         // model tables, same expressions as source/model.cpp:99-122, :62-84
         std::vector<UpdateTables> ht(C); std::vector<double> h8((size_t)C * 8);
         static const int proposal[4][3] = {{1, 2, 3}, {0, 2, 3}, {0, 1, 3}, {0, 1, 2}};
@@ -433,17 +416,17 @@ struct Engine {
             }
             for (int f = 0; f < 4; ++f) { ht[c].ev[f] = std::exp(g[c] * eta[f]); ht[c].iev[f] = std::exp(-g[c] * eta[f]); h8[(size_t)c * 8 + f] = ht[c].ev[f]; h8[(size_t)c * 8 + 4 + f] = ht[c].iev[f]; }
         }
-        DQ_HIP(hipMemcpyAsync(tabs, ht.data(), sizeof(UpdateTables) * C, hipMemcpyHostToDevice, s));
-        DQ_HIP(hipMemcpyAsync(tab8, h8.data(), sizeof(double) * C * 8, hipMemcpyHostToDevice, s));
-        DQ_TRY(launch_build_expv(fields, (long)nt * n, nt, n, tab8, expv, invexpv, (long)nt * n, C, s));
+        DQ_HIP(hipMemcpyAsync(tabs.get(), ht.data(), sizeof(UpdateTables) * C, hipMemcpyHostToDevice, s));
+        DQ_HIP(hipMemcpyAsync(tab8.get(), h8.data(), sizeof(double) * C * 8, hipMemcpyHostToDevice, s));
+        DQ_TRY(launch_build_expv(fields.get(), (long)nt * n, nt, n, tab8.get(), expv.get(), invexpv.get(), (long)nt * n, C, s));
         DQ_HIP(hipStreamSynchronize(s));
         return 0;
     }
 
     // one launch of the checkerboard kernel on this engine's pair tables (chains / par_stride differ for the batched initialisation)
     int cb_apply(CMat in, Mat out, Mat outT, bool reverse, bool inverse, CVec rs_in, CVec cs_in, CVec rs_out, CVec cs_out, int chains, long par_stride) {
-        CbDesc d; d.in = in; d.out = out; d.outT = outT; d.partner = cb_partner; d.n_groups = cb_groups; d.reverse = reverse ? 1 : 0; d.inverse = inverse ? 1 : 0;
-        d.par = cb_par; d.par_stride = par_stride; d.rs_in = rs_in; d.cs_in = cs_in; d.rs_out = rs_out; d.cs_out = cs_out; d.n = n;
+        CbDesc d; d.in = in; d.out = out; d.outT = outT; d.partner = cb_partner.get(); d.n_groups = cb_groups; d.reverse = reverse ? 1 : 0; d.inverse = inverse ? 1 : 0;
+        d.par = cb_par.get(); d.par_stride = par_stride; d.rs_in = rs_in; d.cs_in = cs_in; d.rs_out = rs_out; d.cs_out = cs_out; d.n = n;
         return launch_cb_apply(d, chains, s);
     }
     // dqmc_set_checkerboard: pair tables to the device, then E and E^-1 as dense matrices (the kernel applied to I) for the
@@ -470,16 +453,16 @@ struct Engine {
             par[4 * c] = ch[c]; par[4 * c + 1] = sh[c]; par[4 * c + 2] = f[c]; par[4 * c + 3] = 1.0 / f[c];
         }
         DQ_HIP(hipStreamSynchronize(s));
-        if (cb_partner) { (void)hipFree(cb_partner); cb_partner = nullptr; }
-        DQ_TRY(dalloc(&cb_partner, partner.size()));
-        if (!cb_par) DQ_TRY(dalloc(&cb_par, (size_t)C * 4));
-        DQ_HIP(hipMemcpy(cb_partner, partner.data(), sizeof(int) * partner.size(), hipMemcpyHostToDevice));
-        DQ_HIP(hipMemcpy(cb_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice));
-        cb_groups = n_groups; cb = true;
-        Mat id{bb0, nn};
+        if (!cb_par) DQ_TRY(dev_alloc(cb_par, (size_t)C * 4));
+        DevPtr<int> pt;                                                 // the engine keeps its old table until the new one is on the device
+        DQ_TRY(dev_alloc(pt, partner.size()));
+        DQ_HIP(hipMemcpy(pt.get(), partner.data(), sizeof(int) * partner.size(), hipMemcpyHostToDevice));
+        DQ_HIP(hipMemcpy(cb_par.get(), par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice));
+        cb_partner = std::move(pt); cb_groups = n_groups; cb = true;
+        Mat id{bb0.get(), nn};
         DQ_TRY(launch_set_identity(id, n, C, s));
-        DQ_TRY(cb_apply(id, Mat{expK, nn}, Mat{nullptr, 0}, false, false, CVec(), CVec(), CVec(), CVec(), C, 4));      // E = f E_{G-1} ... E_0
-        DQ_TRY(cb_apply(id, Mat{invexpK, nn}, Mat{nullptr, 0}, true, true, CVec(), CVec(), CVec(), CVec(), C, 4));     // E^-1 = E_0^-1 ... E_{G-1}^-1 / f
+        DQ_TRY(cb_apply(id, Mat{expK.get(), nn}, Mat{nullptr, 0}, false, false, CVec(), CVec(), CVec(), CVec(), C, 4)); // E = f E_{G-1} ... E_0
+        DQ_TRY(cb_apply(id, Mat{invexpK.get(), nn}, Mat{nullptr, 0}, true, true, CVec(), CVec(), CVec(), CVec(), C, 4)); // E^-1 = E_0^-1 ... E_{G-1}^-1 / f
         stack_valid = false; gt_valid = false; ut_valid = false;
         DQ_HIP(hipStreamSynchronize(s));
         return 0;
@@ -488,11 +471,11 @@ struct Engine {
     // DQMC::calculate_Bbar (source/dqmc.cpp:88-105) without the multiply by I: result in *out
     int Bbar(int is, Mat* out) {
         const int l0 = is * n_stab;
-        Mat cur{bb0, nn}, nxt{bb1, nn};
-        DQ_TRY(launch_scale_rows(CMat(expK, nn), ev(l0), cur, n, C, s));                  // B_l0 = diag(expV) expK
+        Mat cur{bb0.get(), nn}, nxt{bb1.get(), nn};
+        DQ_TRY(launch_scale_rows(CMat(expK.get(), nn), ev(l0), cur, n, C, s));            // B_l0 = diag(expV) expK
         for (int loc = 1; loc <= loc_l_end[is]; ++loc) {
             if (cb) DQ_TRY(cb_apply(cur, nxt, Mat{nullptr, 0}, false, false, CVec(), CVec(), ev(l0 + loc), CVec(), C, 4));
-            else DQ_TRY(ctx.gemm(CMat(expK, nn), cur, nxt, ev(l0 + loc)));                // B_l * Bbar
+            else DQ_TRY(ctx.gemm(CMat(expK.get(), nn), cur, nxt, ev(l0 + loc)));          // B_l * Bbar
             std::swap(cur, nxt);
         }
         *out = cur; return 0;
@@ -505,53 +488,50 @@ struct Engine {
         // per block on its own CU (20 x 0.84 ms side by side instead of in a row) -- and only the n_stack - 1 ldr_mul_ldr products,
         // which are a chain, stay sequential.  Halves the cost of an initialisation, i.e. of a replica-exchange round.
         if (C == 1 && n <= 256 && nt % n_stab == 0 && n_stack >= 2) return init_batched();
-        LdrRef tmp{Mat{tmpL, nn}, Vec{tmpD, (long)n}, Mat{tmpR, nn}};
+        const LdrRef tmp = spare.at(0);
         for (int i = n_stack - 1; i >= 0; --i) {
             Mat bb; DQ_TRY(Bbar(i, &bb));
-            if (i == n_stack - 1) DQ_TRY(ctx.to_ldr(bb, stk(i)));
-            else { DQ_TRY(ctx.to_ldr(bb, tmp)); DQ_TRY(ctx.ldr_mul_ldr(stk(i + 1), tmp, stk(i))); }
+            if (i == n_stack - 1) DQ_TRY(ctx.to_ldr(bb, stack.at(i)));
+            else { DQ_TRY(ctx.to_ldr(bb, tmp)); DQ_TRY(ctx.ldr_mul_ldr(stack.at(i + 1), tmp, stack.at(i))); }
         }
         stack_valid = true;
         gt_valid = false;
-        return ctx.inv_I_plus_ldr(stk(0), mG(), logdet);
+        return ctx.inv_I_plus_ldr(stack.at(0), mG(), logdet.get());
     }
     int init_batched() {
         const int S = n_stack;
-        if (!ibuf) {
-            DQ_TRY(dalloc(&ibuf, (size_t)4 * S * nn + (size_t)2 * S * n));
-            DQ_TRY(dalloc(&ijp, (size_t)S * n));
+        if (!ib.tau) {
+            InitBatch b; DQ_TRY(dev_alloc(b.bb, (size_t)2 * S * nn)); DQ_TRY(dev_alloc(b.tau, (size_t)S * n)); DQ_TRY(b.f.alloc(S, n, 1));
+            ib = std::move(b);
         }
-        double* ib0 = ibuf; double* ib1 = ib0 + (size_t)S * nn; double* iL = ib1 + (size_t)S * nn; double* iR = iL + (size_t)S * nn;
-        double* iD = iR + (size_t)S * nn; double* iTau = iD + (size_t)S * n;
         const long bstride = (long)n_stab * n;                                            // exp(V) of block i starts n_stab slices further
-        Mat cur{ib0, nn}, nxt{ib1, nn};
-        DQ_TRY(launch_scale_rows(CMat(expK, 0), CVec(expv, bstride), cur, n, S, s));        // B_l0 of every block
+        Mat cur{ib.bb.get(), nn}, nxt{ib.bb.get() + (size_t)S * nn, nn};
+        DQ_TRY(launch_scale_rows(CMat(expK.get(), 0), CVec(expv.get(), bstride), cur, n, S, s)); // B_l0 of every block
         for (int loc = 1; loc < n_stab; ++loc) {
-            if (cb) DQ_TRY(cb_apply(cur, nxt, Mat{nullptr, 0}, false, false, CVec(), CVec(), CVec(expv + (long)loc * n, bstride), CVec(), S, 0));
+            if (cb) DQ_TRY(cb_apply(cur, nxt, Mat{nullptr, 0}, false, false, CVec(), CVec(), CVec(expv.get() + (long)loc * n, bstride), CVec(), S, 0));
             else {
-                GemmDesc g; g.A = CMat(expK, 0); g.B = cur; g.C = nxt; g.rs = CVec(expv + (long)loc * n, bstride); g.n = n;
+                GemmDesc g; g.A = CMat(expK.get(), 0); g.B = cur; g.C = nxt; g.rs = CVec(expv.get() + (long)loc * n, bstride); g.n = n;
                 DQ_TRY(launch_gemm(g, S, s));                                             // B_l * Bbar, all blocks
             }
             std::swap(cur, nxt);
         }
-        QrWork w{iTau, (long)n, ijp, (long)n};
+        // to_LDR(Bbar_i) for every block, S chains of the same choice as Ctx's minus the panel family (no panel workspace here);
+        // one chain per store, so block i is chain i of the launch
+        const LdrRef all = ib.f.at(0);
+        QrWork w{ib.tau.get(), (long)n, all.jpvt, (long)n};
         w.info = ctx.info();
-        // to_LDR(Bbar_i) for every block, S chains of the same choice as Ctx's minus the panel family (no panel workspace here)
-        DQ_TRY(launch_to_ldr(pick_qr(n, S, false), cur, Mat{iL, nn}, Vec{iD, (long)n}, Mat{iR, nn}, w, n, S, s));
+        DQ_TRY(launch_to_ldr(pick_qr(n, S, false), cur, all.L, all.d, all.R, w, n, S, s));
         // stack[S - 1] = its own factorisation (R a single permuted-triangular factor), then the chain of products
-        LdrRef last = stk(S - 1);
-        DQ_TRY(launch_copy(CMat(iL + (size_t)(S - 1) * nn, nn), last.L, nn, 1, s));
-        DQ_TRY(launch_copy(CMat(iR + (size_t)(S - 1) * nn, nn), last.R, nn, 1, s));
-        DQ_HIP(hipMemcpyAsync(last.d.p, iD + (size_t)(S - 1) * n, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-        DQ_HIP(hipMemcpyAsync(last.jpvt, ijp + (size_t)(S - 1) * n, sizeof(int) * n, hipMemcpyDeviceToDevice, s));
+        const LdrRef last = stack.at(S - 1), own = ib.f.at(S - 1);
+        DQ_TRY(launch_copy(own.L, last.L, nn, 1, s));
+        DQ_TRY(launch_copy(own.R, last.R, nn, 1, s));
+        DQ_HIP(hipMemcpyAsync(last.d.p, own.d.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+        DQ_HIP(hipMemcpyAsync(last.jpvt, own.jpvt, sizeof(int) * n, hipMemcpyDeviceToDevice, s));
         *last.tri = true;
-        for (int i = S - 2; i >= 0; --i) {
-            LdrRef tmp{Mat{iL + (size_t)i * nn, nn}, Vec{iD + (size_t)i * n, (long)n}, Mat{iR + (size_t)i * nn, nn}};
-            DQ_TRY(ctx.ldr_mul_ldr(stk(i + 1), tmp, stk(i)));
-        }
+        for (int i = S - 2; i >= 0; --i) DQ_TRY(ctx.ldr_mul_ldr(stack.at(i + 1), ib.f.at(i), stack.at(i)));
         stack_valid = true;
         gt_valid = false;
-        return ctx.inv_I_plus_ldr(stk(0), mG(), logdet);
+        return ctx.inv_I_plus_ldr(stack.at(0), mG(), logdet.get());
     }
     // DQMC::propagate_GF_forward (source/dqmc.cpp:113-132): G = B_l G B_l^-1
     int wrap_forward(int l) {
@@ -559,11 +539,11 @@ struct Engine {
             // T^T = (E G)^T;  (T E^-1)^T = E^-T T^T with E^-T = E_{G-1}^-1 ... E_0^-1 / f: groups 0 .. G-1, inverse;  G' = diag(ev) (T E^-1) diag(iev)
             DQ_TRY(cb_apply(mG(), Mat{nullptr, 0}, ctx.T(0), false, false, CVec(), CVec(), CVec(), CVec(), C, 4));
             gt_valid = use_gt();
-            return cb_apply(ctx.T(0), Mat{GT, nn}, mG(), false, true, CVec(), CVec(), iev(l), ev(l), C, 4);
+            return cb_apply(ctx.T(0), Mat{GT.get(), nn}, mG(), false, true, CVec(), CVec(), iev(l), ev(l), C, 4);
         }
-        DQ_TRY(ctx.gemm(CMat(expK, nn), mG(), ctx.T(0)));
+        DQ_TRY(ctx.gemm(CMat(expK.get(), nn), mG(), ctx.T(0)));
         gt_valid = use_gt();                                          // the GEMM that writes G writes GT as well
-        return ctx.gemm(ctx.T(0), CMat(invexpK, nn), mG(), ev(l), CVec(), iev(l), 0, 0, use_gt() ? Mat{GT, nn} : Mat{nullptr, 0});
+        return ctx.gemm(ctx.T(0), CMat(invexpK.get(), nn), mG(), ev(l), CVec(), iev(l), 0, 0, use_gt() ? Mat{GT.get(), nn} : Mat{nullptr, 0});
     }
     // The B-bar chain rides on the wraps (single chain, dense kinetic factor, N <= 256: the regime where a 256^3 product IS its launch).
     // calculate_Bbar (source/dqmc.cpp:88-105) is n_stab - 1 dependent products per stabilisation, 5.6 us each of which ~4.5 us are the launch:
@@ -576,18 +556,18 @@ struct Engine {
     // in the backward sweep the chain is associated from the other end.
     bool piggyback() const { return C == 1 && !cb && n <= 256 && pg_eye != nullptr; }
     int wrap_forward_piggy(int l, const double* Pprev, double* Pnext) {
-        GemmDesc g; g.A = CMat(expK, 0); g.B = CMat(G, (long)(Pprev - G)); g.C = Mat{ctx.T(0).p, (long)(Pnext - ctx.T(0).p)};
-        g.rs = CVec(pg_ones, (long)((expv + (long)(l - 1) * n) - pg_ones)); g.n = n;
+        GemmDesc g; g.A = CMat(expK.get(), 0); g.B = CMat(G.get(), (long)(Pprev - G.get())); g.C = Mat{ctx.T(0).p, (long)(Pnext - ctx.T(0).p)};
+        g.rs = CVec(pg_ones.get(), (long)((expv.get() + (long)(l - 1) * n) - pg_ones.get())); g.n = n;
         DQ_TRY(launch_gemm(g, 2, s));
         gt_valid = use_gt();
-        return ctx.gemm(ctx.T(0), CMat(invexpK, nn), mG(), ev(l), CVec(), iev(l), 0, 0, use_gt() ? Mat{GT, nn} : Mat{nullptr, 0});
+        return ctx.gemm(ctx.T(0), CMat(invexpK.get(), nn), mG(), ev(l), CVec(), iev(l), 0, 0, use_gt() ? Mat{GT.get(), nn} : Mat{nullptr, 0});
     }
     int wrap_backward_piggy(int l, const double* Pprev, double* Pnext) {
-        DQ_TRY(ctx.gemm(CMat(invexpK, nn), mG(), ctx.T(0), CVec(), iev(l)));
+        DQ_TRY(ctx.gemm(CMat(invexpK.get(), nn), mG(), ctx.T(0), CVec(), iev(l)));
         gt_valid = use_gt();
-        GemmDesc g; g.A = CMat(ctx.T(0).p, (long)(Pprev - ctx.T(0).p)); g.B = CMat(expK, 0); g.C = Mat{G, (long)(Pnext - G)};
-        g.ks = CVec(expv + (long)l * n, 0); g.n = n;
-        if (use_gt()) g.CT = Mat{GT, (long)(ctx.T(1).p - GT)};          // chain 1's transposed copy goes to scratch
+        GemmDesc g; g.A = CMat(ctx.T(0).p, (long)(Pprev - ctx.T(0).p)); g.B = CMat(expK.get(), 0); g.C = Mat{G.get(), (long)(Pnext - G.get())};
+        g.ks = CVec(expv.get() + (long)l * n, 0); g.n = n;
+        if (use_gt()) g.CT = Mat{GT.get(), (long)(ctx.T(1).p - GT.get())}; // chain 1's transposed copy goes to scratch
         return launch_gemm(g, 2, s);
     }
     // DQMC::propagate_GF_backward (source/dqmc.cpp:169-187): G = B_l^-1 G B_l
@@ -596,18 +576,18 @@ struct Engine {
             // T^T = (E^-1 diag(iev) G diag(ev))^T;  (T E)^T = E^T T^T with E^T = f E_0 ... E_{G-1}: groups G-1 .. 0, forward
             DQ_TRY(cb_apply(mG(), Mat{nullptr, 0}, ctx.T(0), true, true, iev(l), ev(l), CVec(), CVec(), C, 4));
             gt_valid = use_gt();
-            return cb_apply(ctx.T(0), Mat{GT, nn}, mG(), true, false, CVec(), CVec(), CVec(), CVec(), C, 4);
+            return cb_apply(ctx.T(0), Mat{GT.get(), nn}, mG(), true, false, CVec(), CVec(), CVec(), CVec(), C, 4);
         }
-        DQ_TRY(ctx.gemm(CMat(invexpK, nn), mG(), ctx.T(0), CVec(), iev(l)));
+        DQ_TRY(ctx.gemm(CMat(invexpK.get(), nn), mG(), ctx.T(0), CVec(), iev(l)));
         gt_valid = use_gt();
-        return ctx.gemm(ctx.T(0), CMat(expK, nn), mG(), CVec(), ev(l), CVec(), 0, 0, use_gt() ? Mat{GT, nn} : Mat{nullptr, 0});
+        return ctx.gemm(ctx.T(0), CMat(expK.get(), nn), mG(), CVec(), ev(l), CVec(), 0, 0, use_gt() ? Mat{GT.get(), nn} : Mat{nullptr, 0});
     }
     // the walk reads rows of G from a transposed copy: the register walk (n <= 256) and the persistent sub-matrix kernel (any n)
     bool use_gt() const { return n <= 256 || slice_path == SlicePath::PersistentSubmatrix; }     // n > 256: only the persistent sub-matrix kernel reads and maintains GT
     UpdateDesc udesc() const {
-        UpdateDesc d; d.G = mG(); d.fields = fields; d.f_stride = (long)nt * n; d.expv = expv; d.invexpv = invexpv; d.v_stride = (long)nt * n;
-        d.tabs = tabs; d.perm = rs_perm; d.kprop = rs_k; d.u = rs_u; d.rs_stride = (long)nt * n; d.Upanel = Upanel; d.Wpanel = Wpanel; d.Cpanel = Cpanel;
-        d.panel_stride = (long)UPDATE_KD * n; d.state = state; d.state_stride = 4; d.prep = prep; d.prep_stride = 4L * n; d.slice_sync = is_persistent(slice_path) ? slice_sync : nullptr; d.slice_epoch = slice_epoch; d.slice_absent_tile = slice_absent_tile; d.slice_absent_l = slice_absent_l; d.slice_late_tile = slice_late_tile; d.slice_late_us = slice_late_us; d.GT = Mat{GT, nn}; d.gt_valid = gt_valid ? 1 : 0; d.info = ctx.info(); d.acc_out = acc; d.acc_stride = nt; d.n = n; d.nt = nt;
+        UpdateDesc d; d.G = mG(); d.fields = fields.get(); d.f_stride = (long)nt * n; d.expv = expv.get(); d.invexpv = invexpv.get(); d.v_stride = (long)nt * n;
+        d.tabs = tabs.get(); d.perm = rs_perm.get(); d.kprop = rs_k.get(); d.u = rs_u.get(); d.rs_stride = (long)nt * n; d.Upanel = Upanel.get(); d.Wpanel = Wpanel.get(); d.Cpanel = Cpanel.get();
+        d.panel_stride = (long)UPDATE_KD * n; d.state = state.get(); d.state_stride = 4; d.prep = prep.get(); d.prep_stride = 4L * n; d.slice_sync = is_persistent(slice_path) ? slice_sync.get() : nullptr; d.slice_epoch = slice_epoch; d.slice_absent_tile = slice_absent_tile; d.slice_absent_l = slice_absent_l; d.slice_late_tile = slice_late_tile; d.slice_late_us = slice_late_us; d.GT = Mat{GT.get(), nn}; d.gt_valid = gt_valid ? 1 : 0; d.info = ctx.info(); d.acc_out = acc.get(); d.acc_stride = nt; d.n = n; d.nt = nt;
         return d;
     }
     int local_update(int l) {
@@ -619,143 +599,150 @@ struct Engine {
         }
         if (is_persistent(slice_path)) {
             // every launch of a persistent slice kernel gets its own number: the hand-off words carry it, so none has to be re-armed
-            if (++slice_epoch >= SLICE_EPOCH_LIMIT) { DQ_HIP(hipMemsetAsync(slice_sync, 0, (size_t)C * SLICE_SYNC_BYTES, s)); slice_epoch = 1; }
+            if (++slice_epoch >= SLICE_EPOCH_LIMIT) { DQ_HIP(hipMemsetAsync(slice_sync.get(), 0, (size_t)C * SLICE_SYNC_BYTES, s)); slice_epoch = 1; }
         }
         DQ_TRY(launch_update_slice(slice_path, udesc(), l, l, C, s));
         if (profiling) DQ_HIP(hipEventRecord(e1, s));
         return 0;
     }
-    int upload_stream(const int32_t* perm, const uint8_t* kprop, const double* u) {
-        const size_t cnt = (size_t)C * nt * n;
-        if (!perm || !kprop || !u) { set_error("sweep: null random-stream pointer"); return DQMC_EINVAL; }
-        // the device indexes G with perm and the proposal table with kprop: every slice must carry a permutation of the sites and
-        // proposal indices in {0, 1, 2} (what std::shuffle and uniform_int(0, 2) produce, source/update.cpp:14, include/field.h:79)
+    // The random stream of `rows` slices [rows][n], checked in one pass without allocating: the device indexes G with perm and the
+    // proposal table with kprop, so every slice must carry a permutation of the sites and proposal indices in {0, 1, 2} (what
+    // std::shuffle and uniform_int(0, 2) produce, source/update.cpp:14, include/field.h:79).  `who` prefixes the error message.
+    int check_stream(const char* who, const int32_t* perm, const uint8_t* kprop, const double* u, size_t rows) {
+        if (!perm || !kprop || !u) { set_error(std::string(who) + ": null random-stream pointer"); return DQMC_EINVAL; }
         seen.assign((size_t)n, 0);
-        for (size_t row = 0; row < (size_t)C * nt; ++row) {
+        for (size_t row = 0; row < rows; ++row) {
             const int32_t* pr = perm + row * n; const uint8_t* kr = kprop + row * n; const unsigned char mark = (unsigned char)(1 + (row & 1));
             if ((row & 1) == 0) std::fill(seen.begin(), seen.end(), 0);
             for (int idx = 0; idx < n; ++idx) {
                 const int32_t i = pr[idx];
-                if (i < 0 || i >= n || seen[i] == mark || kr[idx] > 2) { set_error("sweep: perm is not a permutation of the sites, or kprop > 2"); return DQMC_EINVAL; }
+                if (i < 0 || i >= n || seen[i] == mark || kr[idx] > 2) { set_error(std::string(who) + ": perm is not a permutation of the sites, or kprop > 2"); return DQMC_EINVAL; }
                 seen[i] = mark;
             }
         }
+        return 0;
+    }
+    int upload_stream(const int32_t* perm, const uint8_t* kprop, const double* u) {
+        const size_t cnt = (size_t)C * nt * n;
+        DQ_TRY(check_stream("sweep", perm, kprop, u, (size_t)C * nt));
         DQ_HIP(hipEventSynchronize(stage_free));                   // previous H2D copies out of the staging buffer are done
-        char* base = static_cast<char*>(h_stage);
+        char* base = h_stage.get();
         double* hu = reinterpret_cast<double*>(base);
         int32_t* hp = reinterpret_cast<int32_t*>(base + cnt * sizeof(double));
         uint8_t* hk = reinterpret_cast<uint8_t*>(base + cnt * (sizeof(double) + sizeof(int32_t)));
         std::memcpy(hu, u, cnt * sizeof(double)); std::memcpy(hp, perm, cnt * sizeof(int32_t)); std::memcpy(hk, kprop, cnt);
-        DQ_HIP(hipMemcpyAsync(rs_u, hu, cnt * sizeof(double), hipMemcpyHostToDevice, s));
-        DQ_HIP(hipMemcpyAsync(rs_perm, hp, cnt * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        DQ_HIP(hipMemcpyAsync(rs_k, hk, cnt, hipMemcpyHostToDevice, s));
+        DQ_HIP(hipMemcpyAsync(rs_u.get(), hu, cnt * sizeof(double), hipMemcpyHostToDevice, s));
+        DQ_HIP(hipMemcpyAsync(rs_perm.get(), hp, cnt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        DQ_HIP(hipMemcpyAsync(rs_k.get(), hk, cnt, hipMemcpyHostToDevice, s));
         DQ_HIP(hipEventRecord(stage_free, s));
         return 0;
     }
     // DQMC::sweep_0_to_beta (source/dqmc.cpp:337-396)
     int sweep_fwd() {
         int n_err = 0;
-        DQ_HIP(hipMemsetAsync(err, 0, sizeof(double) * C * n_stack, s));             // max_abs_diff folds into zeroed slots
+        DQ_HIP(hipMemsetAsync(err.get(), 0, sizeof(double) * C * n_stack, s));       // max_abs_diff folds into zeroed slots
         const bool pg = piggyback();
-        double* Pcur = bb0; double* Pnxt = bb1;
+        double* Pcur = bb0.get(); double* Pnxt = bb1.get();
         for (int l = 0; l < nt; ++l) {
             const int is = stack_idx(l), loc = local_l(l);
-            if (pg && loc >= 1) { DQ_TRY(wrap_forward_piggy(l, loc == 1 ? pg_eye : Pcur, Pnxt)); std::swap(Pcur, Pnxt); }   // P = B_{l-1} ... B_{l0}
+            if (pg && loc >= 1) { DQ_TRY(wrap_forward_piggy(l, loc == 1 ? pg_eye.get() : Pcur, Pnxt)); std::swap(Pcur, Pnxt); } // P = B_{l-1} ... B_{l0}
             else DQ_TRY(wrap_forward(l));
             DQ_TRY(local_update(l));
             if (loc == loc_l_end[is]) {
                 std::swap(G, Gtmp);                                                          // the wrapped G is kept for check_error, the stabilised one is written into the other buffer (no copy)
                 Mat bb;
                 if (pg) {                                                                     // the block's last factor, whose slice has only now been updated
-                    if (loc == 0) DQ_TRY(launch_scale_rows(CMat(expK, nn), ev(l), Mat{Pnxt, nn}, n, C, s));
-                    else DQ_TRY(ctx.gemm(CMat(expK, nn), CMat(Pcur, nn), Mat{Pnxt, nn}, ev(l)));
+                    if (loc == 0) DQ_TRY(launch_scale_rows(CMat(expK.get(), nn), ev(l), Mat{Pnxt, nn}, n, C, s));
+                    else DQ_TRY(ctx.gemm(CMat(expK.get(), nn), CMat(Pcur, nn), Mat{Pnxt, nn}, ev(l)));
                     std::swap(Pcur, Pnxt); bb = Mat{Pcur, nn};
                 } else DQ_TRY(Bbar(is, &bb));
-                if (is == 0) DQ_TRY(ctx.to_ldr(bb, stk(0)));                                  // update_stack_forward :134-146
-                else DQ_TRY(ctx.mat_mul_ldr(bb, stk(is - 1), stk(is)));
+                if (is == 0) DQ_TRY(ctx.to_ldr(bb, stack.at(0)));                                  // update_stack_forward :134-146
+                else DQ_TRY(ctx.mat_mul_ldr(bb, stack.at(is - 1), stack.at(is)));
                 gt_valid = false;                                                            // G is replaced below
-                if (l == nt - 1) DQ_TRY(ctx.inv_I_plus_ldr(stk(is), mG(), logdet));           // stabilize_GF_forward :148-161
-                else DQ_TRY(ctx.inv_I_plus_ldr_mul_ldr(stk(is), stk(is + 1), mG()));
-                DQ_TRY(launch_max_abs_diff(CMat(Gtmp, nn), mG(), err + n_err, n_stack, n, C, s));   // check_error :317-329
+                if (l == nt - 1) DQ_TRY(ctx.inv_I_plus_ldr(stack.at(is), mG(), logdet.get()));           // stabilize_GF_forward :148-161
+                else DQ_TRY(ctx.inv_I_plus_ldr_mul_ldr(stack.at(is), stack.at(is + 1), mG()));
+                DQ_TRY(launch_max_abs_diff(CMat(Gtmp.get(), nn), mG(), err.get() + n_err, n_stack, n, C, s)); // check_error :317-329
                 ++n_err;
             }
         }
-        return launch_fold_stats(dstats, acc, nt, nt, err, n_stack, n_err, n, nt, C, s);
+        return launch_fold_stats(dstats.get(), acc.get(), nt, nt, err.get(), n_stack, n_err, n, nt, C, s);
     }
     // DQMC::sweep_beta_to_0 (source/dqmc.cpp:398-456)
     int sweep_bwd() {
         int n_err = 0;
-        DQ_HIP(hipMemsetAsync(err, 0, sizeof(double) * C * n_stack, s));
+        DQ_HIP(hipMemsetAsync(err.get(), 0, sizeof(double) * C * n_stack, s));
         const bool pg = piggyback();
-        double* Pcur = bb0; double* Pnxt = bb1;
+        double* Pcur = bb0.get(); double* Pnxt = bb1.get();
         for (int l = nt - 1; l >= 0; --l) {
             DQ_TRY(local_update(l));
             const int is = stack_idx(l);
-            if (pg) { DQ_TRY(wrap_backward_piggy(l, local_l(l) == loc_l_end[is] ? pg_eye : Pcur, Pnxt)); std::swap(Pcur, Pnxt); }   // P = B_hi ... B_l
+            if (pg) { DQ_TRY(wrap_backward_piggy(l, local_l(l) == loc_l_end[is] ? pg_eye.get() : Pcur, Pnxt)); std::swap(Pcur, Pnxt); } // P = B_hi ... B_l
             else DQ_TRY(wrap_backward(l));
             if (local_l(l) == 0) {
                 std::swap(G, Gtmp);
                 Mat bb;
                 if (pg) bb = Mat{Pcur, nn}; else DQ_TRY(Bbar(is, &bb));
-                if (is == n_stack - 1) DQ_TRY(ctx.to_ldr(bb, stk(is)));                       // update_stack_backward :189-201
-                else DQ_TRY(ctx.ldr_mul_mat(stk(is + 1), bb, stk(is)));
+                if (is == n_stack - 1) DQ_TRY(ctx.to_ldr(bb, stack.at(is)));                       // update_stack_backward :189-201
+                else DQ_TRY(ctx.ldr_mul_mat(stack.at(is + 1), bb, stack.at(is)));
                 gt_valid = false;
-                if (l == 0) DQ_TRY(ctx.inv_I_plus_ldr(stk(is), mG(), logdet));                // stabilize_GF_backward :203-215
-                else DQ_TRY(ctx.inv_I_plus_ldr_mul_ldr(stk(is - 1), stk(is), mG()));
-                DQ_TRY(launch_max_abs_diff(CMat(Gtmp, nn), mG(), err + n_err, n_stack, n, C, s));
+                if (l == 0) DQ_TRY(ctx.inv_I_plus_ldr(stack.at(is), mG(), logdet.get()));                // stabilize_GF_backward :203-215
+                else DQ_TRY(ctx.inv_I_plus_ldr_mul_ldr(stack.at(is - 1), stack.at(is), mG()));
+                DQ_TRY(launch_max_abs_diff(CMat(Gtmp.get(), nn), mG(), err.get() + n_err, n_stack, n, C, s));
                 ++n_err;
             }
         }
-        return launch_fold_stats(dstats, acc, nt, nt, err, n_stack, n_err, n, nt, C, s);
+        return launch_fold_stats(dstats.get(), acc.get(), nt, nt, err.get(), n_stack, n_err, n, nt, C, s);
     }
     // DQMC::sweep_unequalTime (source/dqmc.cpp:458-515) with propagate_unequalTime_GF_forward :223-248, propagate_Bt0_Bbt :250-264,
     // stabilize_unequalTime :266-285.  No Monte Carlo moves: B_l comes from the current fields (what the reference's B_ / invB_
     // caches hold after sweep_beta_to_0), Gtt[0] is the current G, Bbt = stack[i + 1] as the backward sweep left it.
-    Mat utm(int which, int l) const { return Mat{utG[which] + (long)l * C * nn, nn}; }
+    Mat utm(int which, int l) const { return Mat{ut.G[which].get() + (long)l * C * nn, nn}; }
     int sweep_unequal() {
-        if (!utG[0]) {
-            for (int w = 0; w < 3; ++w) DQ_TRY(dalloc(&utG[w], (size_t)(nt + 1) * C * nn));
-            DQ_TRY(dalloc(&utTmp, (size_t)3 * C * nn)); DQ_TRY(dalloc(&utErr, (size_t)C * 3 * n_stack));
+        if (!ut.tmp) {
+            UnequalTime u;
+            for (int w = 0; w < 3; ++w) DQ_TRY(dev_alloc(u.G[w], (size_t)(nt + 1) * C * nn));
+            DQ_TRY(dev_alloc(u.tmp, (size_t)3 * C * nn)); DQ_TRY(dev_alloc(u.err, (size_t)C * 3 * n_stack));
             const size_t mcount = (size_t)C * 3 * (nt + 1) * n;
-            DQ_TRY(dalloc(&utMeasNow, mcount)); DQ_TRY(dalloc(&utMeasSum, mcount)); DQ_HIP(hipMemsetAsync(utMeasSum, 0, sizeof(double) * mcount, s));
-            for (int b = 0; b < 2; ++b) { DQ_TRY(dalloc(&utL[b], C * nn)); DQ_TRY(dalloc(&utD[b], (size_t)C * n)); DQ_TRY(dalloc(&utR[b], C * nn)); DQ_TRY(dalloc(&utP[b], (size_t)C * n)); }
+            DQ_TRY(dev_alloc(u.meas_now, mcount)); DQ_TRY(dev_alloc(u.meas_sum, mcount)); DQ_TRY(u.bt.alloc(2, n, C));
+            DQ_HIP(hipMemsetAsync(u.meas_sum.get(), 0, sizeof(double) * mcount, s));
+            ut = std::move(u);
         }
-        auto bt = [&](int b) { return LdrRef{Mat{utL[b], nn}, Vec{utD[b], (long)n}, Mat{utR[b], nn}, utP[b], &utTri[b]}; };
+        auto bt = [&](int b) { return ut.bt.at(b); };
         int cur = 0, n_err = 0;
-        DQ_HIP(hipMemsetAsync(utErr, 0, sizeof(double) * C * 3 * n_stack, s));
+        DQ_HIP(hipMemsetAsync(ut.err.get(), 0, sizeof(double) * C * 3 * n_stack, s));
         DQ_TRY(launch_copy(mG(), utm(0, 0), nn, C, s));
         for (int l = 0; l < nt; ++l) {
             if (l == 0) {                                                                            // :234-239
                 DQ_TRY(launch_copy(utm(0, 0), utm(1, 0), nn, C, s));
                 DQ_TRY(launch_axpb_identity(utm(0, 0), utm(2, 0), 1.0, -1.0, n, C, s));
             }
-            DQ_TRY(ctx.gemm(CMat(expK, nn), utm(0, l), ctx.T(0)));                                   // :240 Gtt = B Gtt B^-1
-            DQ_TRY(ctx.gemm(ctx.T(0), CMat(invexpK, nn), utm(0, l + 1), ev(l), CVec(), iev(l)));
-            DQ_TRY(ctx.gemm(CMat(expK, nn), utm(1, l), utm(1, l + 1), ev(l)));                       // :241 Gt0 = B Gt0
-            DQ_TRY(ctx.gemm(utm(2, l), CMat(invexpK, nn), utm(2, l + 1), CVec(), CVec(), iev(l)));   // :242 G0t = G0t B^-1
+            DQ_TRY(ctx.gemm(CMat(expK.get(), nn), utm(0, l), ctx.T(0)));                             // :240 Gtt = B Gtt B^-1
+            DQ_TRY(ctx.gemm(ctx.T(0), CMat(invexpK.get(), nn), utm(0, l + 1), ev(l), CVec(), iev(l)));
+            DQ_TRY(ctx.gemm(CMat(expK.get(), nn), utm(1, l), utm(1, l + 1), ev(l)));                 // :241 Gt0 = B Gt0
+            DQ_TRY(ctx.gemm(utm(2, l), CMat(invexpK.get(), nn), utm(2, l + 1), CVec(), CVec(), iev(l))); // :242 G0t = G0t B^-1
             const int is = stack_idx(l);
             if (local_l(l) == loc_l_end[is]) {
-                for (int w = 0; w < 3; ++w) DQ_TRY(launch_copy(utm(w, l + 1), Mat{utTmp + (long)w * C * nn, nn}, nn, C, s));
+                for (int w = 0; w < 3; ++w) DQ_TRY(launch_copy(utm(w, l + 1), Mat{ut.tmp.get() + (long)w * C * nn, nn}, nn, C, s));
                 Mat bb; DQ_TRY(Bbar(is, &bb));
                 if (is == 0) DQ_TRY(ctx.to_ldr(bb, bt(cur)));                                        // :255-259
                 else { DQ_TRY(ctx.mat_mul_ldr(bb, bt(cur), bt(cur ^ 1))); cur ^= 1; }
                 if (l == nt - 1) {                                                                   // :267-276
-                    DQ_TRY(ctx.inv_I_plus_ldr(bt(cur), utm(0, l + 1), logdet));
+                    DQ_TRY(ctx.inv_I_plus_ldr(bt(cur), utm(0, l + 1), logdet.get()));
                     DQ_TRY(launch_axpb_identity(utm(0, l + 1), utm(1, l + 1), -1.0, 1.0, n, C, s));
                     DQ_TRY(launch_axpb_identity(utm(0, l + 1), utm(2, l + 1), -1.0, 0.0, n, C, s));
                 } else {                                                                             // :278-282, Bbt = stack[is + 1]
-                    DQ_TRY(ctx.inv_I_plus_ldr_mul_ldr(bt(cur), stk(is + 1), utm(0, l + 1)));
-                    DQ_TRY(ctx.inv_invldr_plus_ldr(bt(cur), stk(is + 1), utm(1, l + 1), false));
-                    DQ_TRY(ctx.inv_invldr_plus_ldr(stk(is + 1), bt(cur), utm(2, l + 1), true));
+                    DQ_TRY(ctx.inv_I_plus_ldr_mul_ldr(bt(cur), stack.at(is + 1), utm(0, l + 1)));
+                    DQ_TRY(ctx.inv_invldr_plus_ldr(bt(cur), stack.at(is + 1), utm(1, l + 1), false));
+                    DQ_TRY(ctx.inv_invldr_plus_ldr(stack.at(is + 1), bt(cur), utm(2, l + 1), true));
                 }
                 for (int w = 0; w < 3; ++w) {                                                        // check_error x 3, :502-507
-                    DQ_TRY(launch_max_abs_diff(CMat(utTmp + (long)w * C * nn, nn), utm(w, l + 1), utErr + n_err, 3L * n_stack, n, C, s));
+                    DQ_TRY(launch_max_abs_diff(CMat(ut.tmp.get() + (long)w * C * nn, nn), utm(w, l + 1), ut.err.get() + n_err, 3L * n_stack, n, C, s));
                     ++n_err;
                 }
             }
         }
         ut_valid = true;
-        return launch_fold_stats(dstats, acc, nt, 0, utErr, 3L * n_stack, n_err, n, nt, C, s);
+        return launch_fold_stats(dstats.get(), acc.get(), nt, 0, ut.err.get(), 3L * n_stack, n_err, n, nt, C, s);
     }
     int sync_and_check() {
         DQ_HIP(hipStreamSynchronize(s));
@@ -767,40 +754,64 @@ struct Engine {
         const int rc = take_status(ctx, &bits);
         if (bits & (DQ_STATUS_HANDOFF | DQ_STATUS_CENSUS)) {        // a persistent slice kernel failed: the kernel pairs from now on
             slice_path = pick_slice_path(n, C, false); gt_valid = false;
-            if (bits & DQ_STATUS_HANDOFF) { (void)hipMemset(slice_sync, 0, (size_t)C * SLICE_SYNC_BYTES); slice_epoch = 0; }
+            if (bits & DQ_STATUS_HANDOFF) { (void)hipMemset(slice_sync.get(), 0, (size_t)C * SLICE_SYNC_BYTES); slice_epoch = 0; }
         }
         return rc;
     }
+    // the HS fields in the order of the ABI, [C][n][nt] (an arma::imat nt x n per chain); the device keeps them as [C][nt][n]
+    int download_fields(std::vector<int8_t>& f) const {
+        std::vector<int8_t> dev((size_t)C * nt * n);
+        DQ_HIP(hipMemcpy(dev.data(), fields.get(), dev.size(), hipMemcpyDeviceToHost));
+        f.resize(dev.size());
+        for (int c = 0; c < C; ++c) for (int i = 0; i < n; ++i) for (int l = 0; l < nt; ++l)
+            f[(size_t)c * nt * n + l + (size_t)nt * i] = dev[(size_t)c * nt * n + (size_t)l * n + i];
+        return 0;
+    }
+    // equal-time observables [C][3 + n] on the device -> scalars [C][3], chi_r [C][n] (either may be null)
+    int copy_out_equal_time(const double* src, double* scalars, double* chi_r) const {
+        const size_t w = 3 + (size_t)n;
+        std::vector<double> tmp((size_t)C * w);
+        DQ_HIP(hipMemcpy(tmp.data(), src, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+        for (int c = 0; c < C; ++c) {
+            if (scalars) std::copy(tmp.begin() + c * w, tmp.begin() + c * w + 3, scalars + 3 * (size_t)c);
+            if (chi_r) std::copy(tmp.begin() + c * w + 3, tmp.begin() + (c + 1) * w, chi_r + (size_t)c * n);
+        }
+        return 0;
+    }
 };
 
-// ---- stateless calls: one cached single-chain context per n --------------------------------
+// ---- stateless calls: one cached single-chain context per n, with the inputs and outputs of the calls --------------------------------
+struct Stateless {
+    Ctx ctx;                                   // declared first: its stream outlives the scratch below
+    LdrStore ldr;                              // 3 triples: two uploaded factors (0, 1) and the result (2)
+    DevPtr<double> mats;                       // 4 n x n matrices M(0) .. M(3): uploaded operands and results
+    DevPtr<double> logdet;                     // 1: log|det| of dqmc_inv_I_plus_ldr
+    Mat M(int k) const { return Mat{mats.get() + k * ctx.nn, ctx.nn}; }
+};
 static std::mutex g_ctx_mu;
-static std::map<int, std::unique_ptr<Ctx>> g_ctx;
-static std::map<int, double*> g_ctx_extra;     // 3 LDR triples worth of scratch per n
+static std::map<int, std::unique_ptr<Stateless>> g_ctx;
 
-static int get_ctx(int n, Ctx** out, double** extra) {
+static int get_ctx(int n, Stateless** out) {
     if (n <= 0) { set_error("n must be positive"); return DQMC_EINVAL; }
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { set_error("no HIP device available: this library requires a gfx950 GPU"); return DQMC_ENODEVICE; }
     auto it = g_ctx.find(n);
     if (it == g_ctx.end()) {
-        std::unique_ptr<Ctx> c(new Ctx);
-        DQ_TRY(c->init(n, 1, 0));
-        double* ex = nullptr;
-        DQ_HIP(hipMalloc(&ex, sizeof(double) * (8L * n * n + 4L * n)));
-        g_ctx_extra[n] = ex;
-        it = g_ctx.emplace(n, std::move(c)).first;
+        std::unique_ptr<Stateless> x(new Stateless);
+        DQ_TRY(x->ctx.init(n, 1, 0));
+        DQ_TRY(x->ldr.alloc(3, n, 1)); DQ_TRY(dev_alloc(x->mats, 4L * n * n)); DQ_TRY(dev_alloc(x->logdet, 1));
+        it = g_ctx.emplace(n, std::move(x)).first;
     }
-    *out = it->second.get(); *extra = g_ctx_extra[n];
+    *out = it->second.get();
     return hipSetDevice(0) == hipSuccess ? 0 : DQMC_ENODEVICE;
 }
-struct HostLdr { const double* L; const double* d; const double* R; };
-static int upload_ldr(Ctx* c, double* base, HostLdr h, LdrRef* out) {
-    const long nn = c->nn; const int n = c->n;
-    out->L = Mat{base, nn}; out->R = Mat{base + nn, nn}; out->d = Vec{base + 2 * nn, (long)n};
-    DQ_HIP(hipMemcpyAsync(out->L.p, h.L, sizeof(double) * nn, hipMemcpyHostToDevice, c->stream));
-    DQ_HIP(hipMemcpyAsync(out->R.p, h.R, sizeof(double) * nn, hipMemcpyHostToDevice, c->stream));
-    DQ_HIP(hipMemcpyAsync(out->d.p, h.d, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+// triple k of the stateless scratch receives a factor from the host: its R is not known to be a single QR factor
+static int upload_ldr(Stateless* x, int k, const double* L, const double* d, const double* R, LdrRef* out) {
+    const Ctx& c = x->ctx;
+    *out = x->ldr.at(k); *out->tri = false;
+    DQ_HIP(hipMemcpyAsync(out->L.p, L, sizeof(double) * c.nn, hipMemcpyHostToDevice, c.stream));
+    DQ_HIP(hipMemcpyAsync(out->R.p, R, sizeof(double) * c.nn, hipMemcpyHostToDevice, c.stream));
+    DQ_HIP(hipMemcpyAsync(out->d.p, d, sizeof(double) * c.n, hipMemcpyHostToDevice, c.stream));
     return 0;
 }
 static int download_ldr(Ctx* c, LdrRef f, double* L, double* d, double* R) {
@@ -810,10 +821,6 @@ static int download_ldr(Ctx* c, LdrRef f, double* L, double* d, double* R) {
     DQ_HIP(hipStreamSynchronize(c->stream));
     return take_status(*c);
 }
-static LdrRef slot(Ctx* c, double* extra, int k) {     // k = 0,1,2: LDR-sized scratch slots after the two upload slots
-    double* base = extra + (long)k * (2 * c->nn + c->n);
-    return LdrRef{Mat{base, c->nn}, Vec{base + 2 * c->nn, (long)c->n}, Mat{base + c->nn, c->nn}};
-}
 
 }  // namespace dq
 
@@ -821,32 +828,33 @@ using namespace dq;
 
 struct dqmc_engine { Engine e; };
 
+// the prologue of every engine call: a non-null handle, `e` its engine, the engine's device current
+#define ENGINE_CALL(h) if (!(h)) { set_error("null engine"); return DQMC_EINVAL; } Engine& e = (h)->e; DQ_HIP(hipSetDevice(e.device))
+
 namespace dq {
 int engine_fields_view(dqmc_engine* h, EngineFieldsView* v) {
     if (!h || !v) { set_error("null engine"); return DQMC_EINVAL; }
     Engine& e = h->e;
-    v->device = e.device; v->n = e.n; v->nt = e.nt; v->n_chains = e.C; v->fields = e.fields; v->stream = e.s;
+    v->device = e.device; v->n = e.n; v->nt = e.nt; v->n_chains = e.C; v->fields = e.fields.get(); v->stream = e.s;
     return 0;
 }
 int engine_fields_changed(dqmc_engine* h) {
-    if (!h) { set_error("null engine"); return DQMC_EINVAL; }
-    Engine& e = h->e;
+    ENGINE_CALL(h);
     e.stack_valid = false; e.gt_valid = false;
-    return launch_build_expv(e.fields, (long)e.nt * e.n, e.nt, e.n, e.tab8, e.expv, e.invexpv, (long)e.nt * e.n, e.C, e.s);
+    return launch_build_expv(e.fields.get(), (long)e.nt * e.n, e.nt, e.n, e.tab8.get(), e.expv.get(), e.invexpv.get(), (long)e.nt * e.n, e.C, e.s);
 }
 int engine_exchange_scratch(dqmc_engine* h, int8_t** saved, int8_t** recv, int** tab) {
-    if (!h) { set_error("null engine"); return DQMC_EINVAL; }
-    Engine& e = h->e;
-    if (!e.xsaved) {
-        DQ_TRY(e.dalloc(&e.xsaved, (size_t)e.C * e.nt * e.n)); DQ_TRY(e.dalloc(&e.xrecv, (size_t)2 * e.nt * e.n)); DQ_TRY(e.dalloc(&e.xtab, (size_t)2 * e.C));
+    ENGINE_CALL(h);
+    if (!e.xch.tab) {
+        Engine::Exchange x; DQ_TRY(dev_alloc(x.saved, (size_t)e.C * e.nt * e.n)); DQ_TRY(dev_alloc(x.recv, (size_t)2 * e.nt * e.n)); DQ_TRY(dev_alloc(x.tab, (size_t)2 * e.C));
+        e.xch = std::move(x);
     }
-    *saved = e.xsaved; *recv = e.xrecv; *tab = e.xtab;
+    *saved = e.xch.saved.get(); *recv = e.xch.recv.get(); *tab = e.xch.tab.get();
     return 0;
 }
 }  // namespace dq
 
 #define API_LOCK std::lock_guard<std::mutex> _lk(g_ctx_mu)
-#define CHECK_E(e) if (!(e)) { set_error("null engine"); return DQMC_EINVAL; }
 
 extern "C" {
 
@@ -855,72 +863,72 @@ const char* dqmc_backend(void) { return "hip:gfx950"; }
 int dqmc_device_count(void) { int c = 0; if (hipGetDeviceCount(&c) != hipSuccess) return 0; return c; }
 
 int dqmc_to_ldr(int n, const double* M, double* L, double* d, double* R) {
-    API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
+    API_LOCK; Stateless* x; DQ_TRY(get_ctx(n, &x)); Ctx* c = &x->ctx;
     if (!M || !L || !d || !R) { set_error("null pointer"); return DQMC_EINVAL; }
-    DQ_HIP(hipMemcpyAsync(c->T(5).p, M, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
-    LdrRef out = slot(c, ex, 0);
-    DQ_TRY(c->to_ldr(c->T(5), out));
+    DQ_HIP(hipMemcpyAsync(x->M(0).p, M, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
+    LdrRef out = x->ldr.at(0);
+    DQ_TRY(c->to_ldr(x->M(0), out));
     return download_ldr(c, out, L, d, R);
 }
 int dqmc_ldr_mul_mat(int n, const double* L, const double* d, const double* R, const double* M, double* Lo, double* d_o, double* Ro) {
-    API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
-    LdrRef F; DQ_TRY(upload_ldr(c, slot(c, ex, 0).L.p, HostLdr{L, d, R}, &F));
-    DQ_HIP(hipMemcpyAsync(c->T(5).p, M, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
-    LdrRef out = slot(c, ex, 2);
-    DQ_TRY(c->ldr_mul_mat(F, c->T(5), out));
+    API_LOCK; Stateless* x; DQ_TRY(get_ctx(n, &x)); Ctx* c = &x->ctx;
+    LdrRef F; DQ_TRY(upload_ldr(x, 0, L, d, R, &F));
+    DQ_HIP(hipMemcpyAsync(x->M(0).p, M, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
+    LdrRef out = x->ldr.at(2);
+    DQ_TRY(c->ldr_mul_mat(F, x->M(0), out));
     return download_ldr(c, out, Lo, d_o, Ro);
 }
 int dqmc_mat_mul_ldr(int n, const double* M, const double* L, const double* d, const double* R, double* Lo, double* d_o, double* Ro) {
-    API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
-    LdrRef F; DQ_TRY(upload_ldr(c, slot(c, ex, 0).L.p, HostLdr{L, d, R}, &F));
-    DQ_HIP(hipMemcpyAsync(c->T(5).p, M, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
-    LdrRef out = slot(c, ex, 2);
-    DQ_TRY(c->mat_mul_ldr(c->T(5), F, out));
+    API_LOCK; Stateless* x; DQ_TRY(get_ctx(n, &x)); Ctx* c = &x->ctx;
+    LdrRef F; DQ_TRY(upload_ldr(x, 0, L, d, R, &F));
+    DQ_HIP(hipMemcpyAsync(x->M(0).p, M, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
+    LdrRef out = x->ldr.at(2);
+    DQ_TRY(c->mat_mul_ldr(x->M(0), F, out));
     return download_ldr(c, out, Lo, d_o, Ro);
 }
 int dqmc_ldr_mul_ldr(int n, const double* L1, const double* d1, const double* R1, const double* L2, const double* d2, const double* R2, double* Lo, double* d_o, double* Ro) {
-    API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
-    LdrRef F1, F2; DQ_TRY(upload_ldr(c, slot(c, ex, 0).L.p, HostLdr{L1, d1, R1}, &F1)); DQ_TRY(upload_ldr(c, slot(c, ex, 1).L.p, HostLdr{L2, d2, R2}, &F2));
-    LdrRef out = slot(c, ex, 2);
+    API_LOCK; Stateless* x; DQ_TRY(get_ctx(n, &x)); Ctx* c = &x->ctx;
+    LdrRef F1, F2; DQ_TRY(upload_ldr(x, 0, L1, d1, R1, &F1)); DQ_TRY(upload_ldr(x, 1, L2, d2, R2, &F2));
+    LdrRef out = x->ldr.at(2);
     DQ_TRY(c->ldr_mul_ldr(F1, F2, out));
     return download_ldr(c, out, Lo, d_o, Ro);
 }
 int dqmc_inv_I_plus_ldr(int n, const double* L, const double* d, const double* R, double* G, double* logdet) {
-    API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
-    LdrRef F; DQ_TRY(upload_ldr(c, slot(c, ex, 0).L.p, HostLdr{L, d, R}, &F));
-    DQ_TRY(c->inv_I_plus_ldr(F, c->T(6), c->scal(1)));
-    DQ_HIP(hipMemcpyAsync(G, c->T(6).p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
+    API_LOCK; Stateless* x; DQ_TRY(get_ctx(n, &x)); Ctx* c = &x->ctx;
+    LdrRef F; DQ_TRY(upload_ldr(x, 0, L, d, R, &F));
+    DQ_TRY(c->inv_I_plus_ldr(F, x->M(1), x->logdet.get()));
+    DQ_HIP(hipMemcpyAsync(G, x->M(1).p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
     double ld = 0.0;
-    DQ_HIP(hipMemcpyAsync(&ld, c->scal(1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    DQ_HIP(hipMemcpyAsync(&ld, x->logdet.get(), sizeof(double), hipMemcpyDeviceToHost, c->stream));
     DQ_HIP(hipStreamSynchronize(c->stream));
     if (logdet) *logdet = ld;
     return take_status(*c);
 }
 int dqmc_inv_I_plus_ldr_mul_ldr(int n, const double* L1, const double* d1, const double* R1, const double* L2, const double* d2, const double* R2, double* G) {
-    API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
-    LdrRef F1, F2; DQ_TRY(upload_ldr(c, slot(c, ex, 0).L.p, HostLdr{L1, d1, R1}, &F1)); DQ_TRY(upload_ldr(c, slot(c, ex, 1).L.p, HostLdr{L2, d2, R2}, &F2));
-    DQ_TRY(c->inv_I_plus_ldr_mul_ldr(F1, F2, c->T(6)));
-    DQ_HIP(hipMemcpyAsync(G, c->T(6).p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
+    API_LOCK; Stateless* x; DQ_TRY(get_ctx(n, &x)); Ctx* c = &x->ctx;
+    LdrRef F1, F2; DQ_TRY(upload_ldr(x, 0, L1, d1, R1, &F1)); DQ_TRY(upload_ldr(x, 1, L2, d2, R2, &F2));
+    DQ_TRY(c->inv_I_plus_ldr_mul_ldr(F1, F2, x->M(1)));
+    DQ_HIP(hipMemcpyAsync(G, x->M(1).p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
     DQ_HIP(hipStreamSynchronize(c->stream));
     return take_status(*c);
 }
 int dqmc_gemm(int n, const double* A, int transA, const double* B, int transB, double* Cm) {
-    API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
-    DQ_HIP(hipMemcpyAsync(c->T(5).p, A, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
-    DQ_HIP(hipMemcpyAsync(c->T(6).p, B, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
-    CMat Bm = c->T(6);
-    if (transB) { DQ_TRY(launch_transpose_scale(c->T(6), c->T(7), CVec(), n, 1, c->stream)); Bm = c->T(7); }
-    DQ_TRY(c->gemm(c->T(5), Bm, c->T(8), CVec(), CVec(), CVec(), transA ? 1 : 0));
-    DQ_HIP(hipMemcpyAsync(Cm, c->T(8).p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
+    API_LOCK; Stateless* x; DQ_TRY(get_ctx(n, &x)); Ctx* c = &x->ctx;
+    DQ_HIP(hipMemcpyAsync(x->M(0).p, A, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
+    DQ_HIP(hipMemcpyAsync(x->M(1).p, B, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
+    CMat Bm = x->M(1);
+    if (transB) { DQ_TRY(launch_transpose_scale(x->M(1), x->M(2), CVec(), n, 1, c->stream)); Bm = x->M(2); }
+    DQ_TRY(c->gemm(x->M(0), Bm, x->M(3), CVec(), CVec(), CVec(), transA ? 1 : 0));
+    DQ_HIP(hipMemcpyAsync(Cm, x->M(3).p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
     DQ_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 int dqmc_rank1_update(int n, double* G, int i, double delta) {
-    API_LOCK; Ctx* c; double* ex; DQ_TRY(get_ctx(n, &c, &ex));
+    API_LOCK; Stateless* x; DQ_TRY(get_ctx(n, &x)); Ctx* c = &x->ctx;
     if (i < 0 || i >= n) { set_error("site index out of range"); return DQMC_ERANGE; }
-    DQ_HIP(hipMemcpyAsync(c->T(5).p, G, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
-    DQ_TRY(launch_rank1(c->T(5), i, delta, c->T(6).p, 2L * n + 1, n, 1, c->stream));
-    DQ_HIP(hipMemcpyAsync(G, c->T(5).p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
+    DQ_HIP(hipMemcpyAsync(x->M(0).p, G, sizeof(double) * c->nn, hipMemcpyHostToDevice, c->stream));
+    DQ_TRY(launch_rank1(x->M(0), i, delta, x->M(1).p, 2L * n + 1, n, 1, c->stream));      // scratch: 2n + 1 doubles from M(1) on
+    DQ_HIP(hipMemcpyAsync(G, x->M(0).p, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
     DQ_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -944,14 +952,14 @@ int dqmc_create(dqmc_engine** out, int device, int n_sites, int nt, int n_stab, 
 }
 int dqmc_set_checkerboard(dqmc_engine* h, int n_groups, const int32_t* bonds, const int32_t* group_sizes, const double* cosh_t, const double* sinh_t,
                           const double* diag_factor) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     return e.set_checkerboard(n_groups, bonds, group_sizes, cosh_t, sinh_t, diag_factor);
 }
 void dqmc_destroy(dqmc_engine* h) { if (h) { (void)hipSetDevice(h->e.device); delete h; } }
 int dqmc_n_chains(dqmc_engine* h) { return h ? h->e.C : 0; }
 
 int dqmc_set_fields(dqmc_engine* h, const int64_t* f) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     std::vector<int8_t> tmp((size_t)e.C * e.nt * e.n);
     for (int c = 0; c < e.C; ++c) for (int i = 0; i < e.n; ++i) for (int l = 0; l < e.nt; ++l) {
         const int64_t v = f[(size_t)c * e.nt * e.n + l + (size_t)e.nt * i];
@@ -959,113 +967,104 @@ int dqmc_set_fields(dqmc_engine* h, const int64_t* f) {
         tmp[(size_t)c * e.nt * e.n + (size_t)l * e.n + i] = (int8_t)v;
     }
     DQ_HIP(hipStreamSynchronize(e.s));
-    DQ_HIP(hipMemcpy(e.fields, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-    DQ_TRY(launch_build_expv(e.fields, (long)e.nt * e.n, e.nt, e.n, e.tab8, e.expv, e.invexpv, (long)e.nt * e.n, e.C, e.s));
+    DQ_HIP(hipMemcpy(e.fields.get(), tmp.data(), tmp.size(), hipMemcpyHostToDevice));
+    DQ_TRY(launch_build_expv(e.fields.get(), (long)e.nt * e.n, e.nt, e.n, e.tab8.get(), e.expv.get(), e.invexpv.get(), (long)e.nt * e.n, e.C, e.s));
     DQ_HIP(hipStreamSynchronize(e.s));
     return 0;
 }
 int dqmc_get_fields(dqmc_engine* h, int64_t* f) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     DQ_TRY(e.sync_and_check());
-    std::vector<int8_t> tmp((size_t)e.C * e.nt * e.n);
-    DQ_HIP(hipMemcpy(tmp.data(), e.fields, tmp.size(), hipMemcpyDeviceToHost));
-    for (int c = 0; c < e.C; ++c) for (int i = 0; i < e.n; ++i) for (int l = 0; l < e.nt; ++l)
-        f[(size_t)c * e.nt * e.n + l + (size_t)e.nt * i] = tmp[(size_t)c * e.nt * e.n + (size_t)l * e.n + i];
+    std::vector<int8_t> tmp; DQ_TRY(e.download_fields(tmp));
+    std::copy(tmp.begin(), tmp.end(), f);
     return 0;
 }
-int dqmc_init(dqmc_engine* h) { CHECK_E(h); DQ_HIP(hipSetDevice(h->e.device)); DQ_TRY(h->e.init()); return h->e.sync_and_check(); }
+int dqmc_init(dqmc_engine* h) { ENGINE_CALL(h); DQ_TRY(e.init()); return e.sync_and_check(); }
 int dqmc_get_G(dqmc_engine* h, double* G) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device)); DQ_TRY(e.sync_and_check());
-    DQ_HIP(hipMemcpy(G, e.G, sizeof(double) * e.C * e.nn, hipMemcpyDeviceToHost)); return 0;
+    ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
+    DQ_HIP(hipMemcpy(G, e.G.get(), sizeof(double) * e.C * e.nn, hipMemcpyDeviceToHost)); return 0;
 }
 int dqmc_set_G(dqmc_engine* h, const double* G) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device)); DQ_HIP(hipStreamSynchronize(e.s));
-    DQ_HIP(hipMemcpy(e.G, G, sizeof(double) * e.C * e.nn, hipMemcpyHostToDevice)); e.gt_valid = false; return 0;
+    ENGINE_CALL(h); DQ_HIP(hipStreamSynchronize(e.s));
+    DQ_HIP(hipMemcpy(e.G.get(), G, sizeof(double) * e.C * e.nn, hipMemcpyHostToDevice)); e.gt_valid = false; return 0;
 }
 int dqmc_get_logdet(dqmc_engine* h, double* ld) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device)); DQ_TRY(e.sync_and_check());
-    DQ_HIP(hipMemcpy(ld, e.logdet, sizeof(double) * e.C, hipMemcpyDeviceToHost)); return 0;
+    ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
+    DQ_HIP(hipMemcpy(ld, e.logdet.get(), sizeof(double) * e.C, hipMemcpyDeviceToHost)); return 0;
 }
 int dqmc_n_stack(dqmc_engine* h) { return h ? h->e.n_stack : 0; }
 int dqmc_get_stack(dqmc_engine* h, int i, double* L, double* d, double* R) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (i < 0 || i >= e.n_stack) { set_error("LDR Stack index out of bounds"); return DQMC_ERANGE; }
     if (!e.stack_valid) { set_error("stack not initialised: call dqmc_init first"); return DQMC_EINVAL; }
     DQ_TRY(e.sync_and_check());
-    LdrRef f = e.stk(i);
+    LdrRef f = e.stack.at(i);
     DQ_HIP(hipMemcpy(L, f.L.p, sizeof(double) * e.C * e.nn, hipMemcpyDeviceToHost));
     DQ_HIP(hipMemcpy(R, f.R.p, sizeof(double) * e.C * e.nn, hipMemcpyDeviceToHost));
     DQ_HIP(hipMemcpy(d, f.d.p, sizeof(double) * e.C * e.n, hipMemcpyDeviceToHost));
     return 0;
 }
 int dqmc_sweep_0_to_beta(dqmc_engine* h, const int32_t* perm, const uint8_t* kprop, const double* u) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (!e.stack_valid) { set_error("dqmc_init must be called before sweeping"); return DQMC_EINVAL; }
     DQ_TRY(e.upload_stream(perm, kprop, u)); return e.sweep_fwd();
 }
 int dqmc_sweep_beta_to_0(dqmc_engine* h, const int32_t* perm, const uint8_t* kprop, const double* u) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (!e.stack_valid) { set_error("dqmc_init must be called before sweeping"); return DQMC_EINVAL; }
     DQ_TRY(e.upload_stream(perm, kprop, u)); return e.sweep_bwd();
 }
-int dqmc_sync(dqmc_engine* h) { CHECK_E(h); DQ_HIP(hipSetDevice(h->e.device)); return h->e.sync_and_check(); }
+int dqmc_sync(dqmc_engine* h) { ENGINE_CALL(h); return e.sync_and_check(); }
 int dqmc_get_stats(dqmc_engine* h, dqmc_stats* out) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device)); DQ_TRY(e.sync_and_check());
+    ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
     static_assert(sizeof(DevStats) == sizeof(dqmc_stats), "stats layout");
-    DQ_HIP(hipMemcpy(out, e.dstats, sizeof(DevStats) * e.C, hipMemcpyDeviceToHost)); return 0;
+    DQ_HIP(hipMemcpy(out, e.dstats.get(), sizeof(DevStats) * e.C, hipMemcpyDeviceToHost)); return 0;
 }
 int dqmc_wrap_forward(dqmc_engine* h, int l) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (l < 0 || l >= e.nt) { set_error("time slice out of range"); return DQMC_ERANGE; }
     return e.wrap_forward(l);
 }
 int dqmc_wrap_backward(dqmc_engine* h, int l) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (l < 0 || l >= e.nt) { set_error("time slice out of range"); return DQMC_ERANGE; }
     return e.wrap_backward(l);
 }
 int dqmc_local_update_slice(dqmc_engine* h, int l, const int32_t* perm, const uint8_t* kprop, const double* u, int* accepted) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (l < 0 || l >= e.nt) { set_error("time slice out of range"); return DQMC_ERANGE; }
-    if (!perm || !kprop || !u) { set_error("local_update_slice: null random-stream pointer"); return DQMC_EINVAL; }
-    for (int c = 0; c < e.C; ++c) {                                          // same contract as the sweeps (Engine::upload_stream)
-        std::vector<unsigned char> seen((size_t)e.n, 0);
-        for (int idx = 0; idx < e.n; ++idx) {
-            const int32_t i = perm[(size_t)c * e.n + idx];
-            if (i < 0 || i >= e.n || seen[i] || kprop[(size_t)c * e.n + idx] > 2) { set_error("local_update_slice: perm is not a permutation of the sites, or kprop > 2"); return DQMC_EINVAL; }
-            seen[i] = 1;
-        }
-    }
+    DQ_TRY(e.check_stream("local_update_slice", perm, kprop, u, e.C));       // one slice per chain, same contract as the sweeps
     DQ_HIP(hipStreamSynchronize(e.s));
     for (int c = 0; c < e.C; ++c) {
         const size_t off = ((size_t)c * e.nt + l) * e.n;
-        DQ_HIP(hipMemcpy(e.rs_perm + off, perm + (size_t)c * e.n, sizeof(int32_t) * e.n, hipMemcpyHostToDevice));
-        DQ_HIP(hipMemcpy(e.rs_k + off, kprop + (size_t)c * e.n, e.n, hipMemcpyHostToDevice));
-        DQ_HIP(hipMemcpy(e.rs_u + off, u + (size_t)c * e.n, sizeof(double) * e.n, hipMemcpyHostToDevice));
+        DQ_HIP(hipMemcpy(e.rs_perm.get() + off, perm + (size_t)c * e.n, sizeof(int32_t) * e.n, hipMemcpyHostToDevice));
+        DQ_HIP(hipMemcpy(e.rs_k.get() + off, kprop + (size_t)c * e.n, e.n, hipMemcpyHostToDevice));
+        DQ_HIP(hipMemcpy(e.rs_u.get() + off, u + (size_t)c * e.n, sizeof(double) * e.n, hipMemcpyHostToDevice));
     }
     DQ_TRY(e.local_update(l));
-    DQ_TRY(launch_fold_stats(e.dstats, e.acc + l, e.nt, 1, e.err, e.n_stack, 0, e.n, e.nt, e.C, e.s));
+    DQ_TRY(launch_fold_stats(e.dstats.get(), e.acc.get() + l, e.nt, 1, e.err.get(), e.n_stack, 0, e.n, e.nt, e.C, e.s));
     DQ_TRY(e.sync_and_check());
-    if (accepted) for (int c = 0; c < e.C; ++c) DQ_HIP(hipMemcpy(accepted + c, e.acc + (size_t)c * e.nt + l, sizeof(int), hipMemcpyDeviceToHost));
+    if (accepted) for (int c = 0; c < e.C; ++c) DQ_HIP(hipMemcpy(accepted + c, e.acc.get() + (size_t)c * e.nt + l, sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 int dqmc_calculate_Bbar(dqmc_engine* h, int is, double* out) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (is < 0 || is >= e.n_stack) { set_error("stack index out of range"); return DQMC_ERANGE; }
     Mat bb; DQ_TRY(e.Bbar(is, &bb)); DQ_HIP(hipStreamSynchronize(e.s));
     DQ_HIP(hipMemcpy(out, bb.p, sizeof(double) * e.C * e.nn, hipMemcpyDeviceToHost)); return 0;
 }
 // AttractiveHubbard::global_action (source/model.cpp:140-159); the field sums run on the host copy
 int dqmc_global_action(dqmc_engine* h, double* S) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device)); DQ_TRY(e.sync_and_check());
-    std::vector<int8_t> tmp((size_t)e.C * e.nt * e.n); std::vector<double> ld(e.C);
-    DQ_HIP(hipMemcpy(tmp.data(), e.fields, tmp.size(), hipMemcpyDeviceToHost));
-    DQ_HIP(hipMemcpy(ld.data(), e.logdet, sizeof(double) * e.C, hipMemcpyDeviceToHost));
+    ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
+    std::vector<int8_t> tmp; std::vector<double> ld(e.C);
+    DQ_TRY(e.download_fields(tmp));
+    DQ_HIP(hipMemcpy(ld.data(), e.logdet.get(), sizeof(double) * e.C, hipMemcpyDeviceToHost));
     const double alpha = -1.0;
+    const size_t per = (size_t)e.nt * e.n;
     for (int c = 0; c < e.C; ++c) {
         double lb = 0.0, lg = 0.0;
-        for (int i = 0; i < e.n; ++i) for (int l = 0; l < e.nt; ++l) {     // arma::imat memory order
-            const int f = tmp[(size_t)c * e.nt * e.n + (size_t)l * e.n + i];
+        for (size_t k = 0; k < per; ++k) {                                // arma::imat memory order
+            const int f = tmp[c * per + k];
             lb += alpha * e.g_host[c] * e.eta_host[f]; lg += std::log(e.gamma_host[f]);
         }
         S[c] = -2.0 * ld[c] - (lb + lg);
@@ -1073,98 +1072,87 @@ int dqmc_global_action(dqmc_engine* h, double* S) {
     return 0;
 }
 int dqmc_sweep_unequal_time(dqmc_engine* h) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (!e.stack_valid) { set_error("sweep_unequal_time: call dqmc_init first"); return DQMC_EINVAL; }
     return e.sweep_unequal();
 }
 int dqmc_get_G_tau(dqmc_engine* h, int which, int l, double* out) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (which < 0 || which > 2 || l < 0 || l > e.nt) { set_error("get_G_tau: which in 0..2, l in 0..nt"); return DQMC_ERANGE; }
     if (!e.ut_valid) { set_error("get_G_tau: run dqmc_sweep_unequal_time first"); return DQMC_EINVAL; }
     DQ_TRY(e.sync_and_check());
-    DQ_HIP(hipMemcpy(out, e.utG[which] + (long)l * e.C * e.nn, sizeof(double) * e.C * e.nn, hipMemcpyDeviceToHost));
+    DQ_HIP(hipMemcpy(out, e.utm(which, l).p, sizeof(double) * e.C * e.nn, hipMemcpyDeviceToHost));
     return 0;
 }
 // DQMC::half_warp (source/dqmc.cpp:288-315): invexpK_half * M * expK_half, two GEMMs on the engine's stream
 int dqmc_half_warp(dqmc_engine* h, const double* expK_half, const double* invexpK_half, int which, int l, double* out) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (!out) { set_error("half_warp: out is NULL"); return DQMC_EINVAL; }
     if (which < -1 || which > 2 || (which >= 0 && (l < 0 || l > e.nt))) { set_error("half_warp: which in -1..2, l in 0..nt"); return DQMC_ERANGE; }
     if (which >= 0 && !e.ut_valid) { set_error("half_warp: run dqmc_sweep_unequal_time first"); return DQMC_EINVAL; }
     if ((expK_half == nullptr) != (invexpK_half == nullptr)) { set_error("half_warp: pass both half-step matrices or neither"); return DQMC_EINVAL; }
     if (expK_half) {
-        if (!e.expKh) { DQ_TRY(e.dalloc(&e.expKh, e.nn)); DQ_TRY(e.dalloc(&e.invexpKh, e.nn)); DQ_TRY(e.dalloc(&e.hwOut, (size_t)e.C * e.nn)); }
+        if (!e.hw.out) { Engine::HalfWarp x; DQ_TRY(dev_alloc(x.expK, e.nn)); DQ_TRY(dev_alloc(x.invexpK, e.nn)); DQ_TRY(dev_alloc(x.out, (size_t)e.C * e.nn)); e.hw = std::move(x); }
         DQ_HIP(hipStreamSynchronize(e.s));                         // pageable host memory: the copies below are synchronous with respect to the host
-        DQ_HIP(hipMemcpy(e.expKh, expK_half, sizeof(double) * e.nn, hipMemcpyHostToDevice));
-        DQ_HIP(hipMemcpy(e.invexpKh, invexpK_half, sizeof(double) * e.nn, hipMemcpyHostToDevice));
-    } else if (!e.expKh) { set_error("half_warp: no half-step matrices uploaded yet"); return DQMC_EINVAL; }
-    const CMat M = which < 0 ? CMat(e.G, e.nn) : CMat(e.utG[which] + (long)l * e.C * e.nn, e.nn);
-    DQ_TRY(e.ctx.gemm(CMat(e.invexpKh, 0), M, e.ctx.T(0)));                     // chain stride 0: one matrix for every chain
-    DQ_TRY(e.ctx.gemm(e.ctx.T(0), CMat(e.expKh, 0), Mat{e.hwOut, e.nn}));
+        DQ_HIP(hipMemcpy(e.hw.expK.get(), expK_half, sizeof(double) * e.nn, hipMemcpyHostToDevice));
+        DQ_HIP(hipMemcpy(e.hw.invexpK.get(), invexpK_half, sizeof(double) * e.nn, hipMemcpyHostToDevice));
+    } else if (!e.hw.out) { set_error("half_warp: no half-step matrices uploaded yet"); return DQMC_EINVAL; }
+    const CMat M = which < 0 ? CMat(e.mG()) : CMat(e.utm(which, l));
+    DQ_TRY(e.ctx.gemm(CMat(e.hw.invexpK.get(), 0), M, e.ctx.T(0)));                // chain stride 0: one matrix for every chain
+    DQ_TRY(e.ctx.gemm(e.ctx.T(0), CMat(e.hw.expK.get(), 0), Mat{e.hw.out.get(), e.nn}));
     DQ_TRY(e.sync_and_check());
-    DQ_HIP(hipMemcpy(out, e.hwOut, sizeof(double) * e.C * e.nn, hipMemcpyDeviceToHost));
+    DQ_HIP(hipMemcpy(out, e.hw.out.get(), sizeof(double) * e.C * e.nn, hipMemcpyDeviceToHost));
     return 0;
 }
 int dqmc_measure_unequal_time(dqmc_engine* h, int L1, int L2, int accumulate, double* out) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (L1 < 1 || L2 < 1 || L1 * L2 != e.n) { set_error("measure_unequal_time: L1*L2 must equal n_sites"); return DQMC_EINVAL; }
     if (!e.ut_valid) { set_error("measure_unequal_time: run dqmc_sweep_unequal_time first"); return DQMC_EINVAL; }
     const long stride = 3L * (e.nt + 1) * e.n;
     if (accumulate) {
-        DQ_TRY(launch_measure_unequal_time(e.utG[0], e.utG[1], e.utG[2], e.utMeasSum, stride, L1, L2, e.nt, 1, e.C, e.s));
+        DQ_TRY(launch_measure_unequal_time(e.ut.G[0].get(), e.ut.G[1].get(), e.ut.G[2].get(), e.ut.meas_sum.get(), stride, L1, L2, e.nt, 1, e.C, e.s));
         ++e.ut_meas_count; return 0;
     }
     if (!out) { set_error("measure_unequal_time: out is NULL"); return DQMC_EINVAL; }
-    DQ_TRY(launch_measure_unequal_time(e.utG[0], e.utG[1], e.utG[2], e.utMeasNow, stride, L1, L2, e.nt, 0, e.C, e.s));
+    DQ_TRY(launch_measure_unequal_time(e.ut.G[0].get(), e.ut.G[1].get(), e.ut.G[2].get(), e.ut.meas_now.get(), stride, L1, L2, e.nt, 0, e.C, e.s));
     DQ_TRY(e.sync_and_check());
-    DQ_HIP(hipMemcpy(out, e.utMeasNow, sizeof(double) * e.C * stride, hipMemcpyDeviceToHost));
+    DQ_HIP(hipMemcpy(out, e.ut.meas_now.get(), sizeof(double) * e.C * stride, hipMemcpyDeviceToHost));
     return 0;
 }
 int dqmc_measure_unequal_fetch(dqmc_engine* h, double* out_sum, int64_t* n_measurements, int reset) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device)); DQ_TRY(e.sync_and_check());
-    if (!e.utMeasSum) { set_error("measure_unequal_fetch: nothing measured yet"); return DQMC_EINVAL; }
+    ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
+    if (!e.ut.meas_sum) { set_error("measure_unequal_fetch: nothing measured yet"); return DQMC_EINVAL; }
     const size_t cnt = (size_t)e.C * 3 * (e.nt + 1) * e.n;
-    if (out_sum) DQ_HIP(hipMemcpy(out_sum, e.utMeasSum, sizeof(double) * cnt, hipMemcpyDeviceToHost));
+    if (out_sum) DQ_HIP(hipMemcpy(out_sum, e.ut.meas_sum.get(), sizeof(double) * cnt, hipMemcpyDeviceToHost));
     if (n_measurements) *n_measurements = e.ut_meas_count;
-    if (reset) { DQ_HIP(hipMemset(e.utMeasSum, 0, sizeof(double) * cnt)); e.ut_meas_count = 0; }
+    if (reset) { DQ_HIP(hipMemset(e.ut.meas_sum.get(), 0, sizeof(double) * cnt)); e.ut_meas_count = 0; }
     return 0;
 }
 int dqmc_measure_equal_time(dqmc_engine* h, int L1, int L2, double* scalars, double* chi_r) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (L1 < 1 || L2 < 1 || L1 * L2 != e.n) { set_error("measure_equal_time: L1*L2 must equal n_sites"); return DQMC_EINVAL; }
-    DQ_TRY(launch_measure_equal_time(CMat(e.G, e.nn), e.meas_now, 3 + e.n, L1, L2, 0, e.C, e.s));
+    DQ_TRY(launch_measure_equal_time(CMat(e.G.get(), e.nn), e.meas_now.get(), 3 + e.n, L1, L2, 0, e.C, e.s));
     DQ_TRY(e.sync_and_check());
-    std::vector<double> tmp((size_t)e.C * (3 + e.n));
-    DQ_HIP(hipMemcpy(tmp.data(), e.meas_now, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
-    for (int c = 0; c < e.C; ++c) {
-        if (scalars) std::copy(tmp.begin() + (size_t)c * (3 + e.n), tmp.begin() + (size_t)c * (3 + e.n) + 3, scalars + 3 * (size_t)c);
-        if (chi_r) std::copy(tmp.begin() + (size_t)c * (3 + e.n) + 3, tmp.begin() + (size_t)(c + 1) * (3 + e.n), chi_r + (size_t)c * e.n);
-    }
-    return 0;
+    return e.copy_out_equal_time(e.meas_now.get(), scalars, chi_r);
 }
 int dqmc_measure_accumulate(dqmc_engine* h, int L1, int L2) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     if (L1 < 1 || L2 < 1 || L1 * L2 != e.n) { set_error("measure_accumulate: L1*L2 must equal n_sites"); return DQMC_EINVAL; }
-    DQ_TRY(launch_measure_equal_time(CMat(e.G, e.nn), e.meas_sum, 3 + e.n, L1, L2, 1, e.C, e.s));     // asynchronous, in stream order after the sweep
+    DQ_TRY(launch_measure_equal_time(CMat(e.G.get(), e.nn), e.meas_sum.get(), 3 + e.n, L1, L2, 1, e.C, e.s)); // asynchronous, in stream order after the sweep
     ++e.meas_count;
     return 0;
 }
 int dqmc_measure_fetch(dqmc_engine* h, double* scalars_sum, double* chi_r_sum, int64_t* n_measurements, int reset) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device)); DQ_TRY(e.sync_and_check());
-    std::vector<double> tmp((size_t)e.C * (3 + e.n));
-    DQ_HIP(hipMemcpy(tmp.data(), e.meas_sum, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
-    for (int c = 0; c < e.C; ++c) {
-        if (scalars_sum) std::copy(tmp.begin() + (size_t)c * (3 + e.n), tmp.begin() + (size_t)c * (3 + e.n) + 3, scalars_sum + 3 * (size_t)c);
-        if (chi_r_sum) std::copy(tmp.begin() + (size_t)c * (3 + e.n) + 3, tmp.begin() + (size_t)(c + 1) * (3 + e.n), chi_r_sum + (size_t)c * e.n);
-    }
+    ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
+    DQ_TRY(e.copy_out_equal_time(e.meas_sum.get(), scalars_sum, chi_r_sum));
     if (n_measurements) *n_measurements = e.meas_count;
-    if (reset) { DQ_HIP(hipMemset(e.meas_sum, 0, sizeof(double) * tmp.size())); e.meas_count = 0; }
+    if (reset) { DQ_HIP(hipMemset(e.meas_sum.get(), 0, sizeof(double) * e.C * (3 + e.n))); e.meas_count = 0; }
     return 0;
 }
 int dqmc_update_kernel_time(dqmc_engine* h, double* ms, int64_t* n_launches, int64_t* n_accepted) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device)); DQ_TRY(e.sync_and_check());
+    ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
     std::vector<DevStats> st(e.C);
-    DQ_HIP(hipMemcpy(st.data(), e.dstats, sizeof(DevStats) * e.C, hipMemcpyDeviceToHost));
+    DQ_HIP(hipMemcpy(st.data(), e.dstats.get(), sizeof(DevStats) * e.C, hipMemcpyDeviceToHost));
     long long acc = 0; for (auto& x : st) acc += x.n_accepted;
     if (ms) *ms = e.upd_ms; if (n_launches) *n_launches = e.upd_launches; if (n_accepted) *n_accepted = acc - e.upd_accept_base;
     e.upd_ms = 0.0; e.upd_launches = 0; e.upd_accept_base = acc;
@@ -1173,11 +1161,11 @@ int dqmc_update_kernel_time(dqmc_engine* h, double* ms, int64_t* n_launches, int
 // diagnostic: 1 when the next local update of this engine takes a persistent single-launch slice kernel (Engine::slice_path), 0 for
 // the kernel pairs and the solo kernel
 int dqmc_debug_snapshot(dqmc_engine* h, double* wrap_err, int* accepted, unsigned int* sync_words, unsigned int* slice_epoch) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device));
+    ENGINE_CALL(h);
     DQ_HIP(hipStreamSynchronize(e.s));
-    if (wrap_err) DQ_HIP(hipMemcpy(wrap_err, e.err, sizeof(double) * e.n_stack, hipMemcpyDeviceToHost));
-    if (accepted) DQ_HIP(hipMemcpy(accepted, e.acc, sizeof(int) * e.nt, hipMemcpyDeviceToHost));
-    if (sync_words) DQ_HIP(hipMemcpy(sync_words, e.slice_sync, sizeof(unsigned int) * 80, hipMemcpyDeviceToHost));
+    if (wrap_err) DQ_HIP(hipMemcpy(wrap_err, e.err.get(), sizeof(double) * e.n_stack, hipMemcpyDeviceToHost));
+    if (accepted) DQ_HIP(hipMemcpy(accepted, e.acc.get(), sizeof(int) * e.nt, hipMemcpyDeviceToHost));
+    if (sync_words) DQ_HIP(hipMemcpy(sync_words, e.slice_sync.get(), sizeof(unsigned int) * 80, hipMemcpyDeviceToHost));
     if (slice_epoch) *slice_epoch = e.slice_epoch;
     return 0;
 }
@@ -1188,13 +1176,13 @@ int dqmc_slice_path(dqmc_engine* h) {
     // 2: at least one launch of the persistent kernel fell back to the solo walk (a flush workgroup had not become resident in time)
     unsigned solo = 0;
     for (int c = 0; c < e.C && !solo; ++c) {
-        SliceSync hs; if (hipMemcpy(&hs, e.slice_sync + (size_t)c * SLICE_SYNC_BYTES, 64, hipMemcpyDeviceToHost) != hipSuccess) break;
+        SliceSync hs; if (hipMemcpy(&hs, e.slice_sync.get() + (size_t)c * SLICE_SYNC_BYTES, 64, hipMemcpyDeviceToHost) != hipSuccess) break;
         solo = hs.solo_count;
     }
     return solo ? 2 : 1;
 }
 int dqmc_set_profiling(dqmc_engine* h, int on) {
-    CHECK_E(h); Engine& e = h->e; DQ_HIP(hipSetDevice(e.device)); DQ_TRY(e.sync_and_check());
+    ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
     e.profiling = on != 0; return 0;
 }
 

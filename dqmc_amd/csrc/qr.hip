@@ -24,8 +24,6 @@
 #include "wave.h"
 #include <cstdlib>
 
-#define DQ_TRY_RC(expr) do { int _rc = (expr); if (_rc != 0) return _rc; } while (0)
-
 namespace dq {
 
 
@@ -380,8 +378,8 @@ static int formq_assemble(Mat A, Mat L, Vec d, Mat R, const QrWork& w, int n, in
     return launch_assemble_r(A, d, R, w, n, n_chains, s);
 }
 static int to_ldr_panel(Mat A, Mat L, Vec d, Mat R, const QrWork& w, int n, int n_chains, hipStream_t s) {
-    DQ_TRY_RC(launch_qr_panel(A, w, n, n_chains, s));
-    DQ_TRY_RC(launch_qr_panel_formq(w, L, n, n_chains, s));
+    DQ_TRY(launch_qr_panel(A, w, n, n_chains, s));
+    DQ_TRY(launch_qr_panel_formq(w, L, n, n_chains, s));
     return launch_assemble_r(A, d, R, w, n, n_chains, s);
 }
 // the single-workgroup streaming kernel with NR rows per lane
@@ -400,10 +398,10 @@ int launch_to_ldr(QrFamily f, Mat A, Mat L, Vec d, Mat R, QrWork w, int n, int n
     case QrFamily::Panel: return to_ldr_panel(A, L, d, R, w, n, n_chains, s);
     case QrFamily::ColumnOwner:
         if (n > 256) break;
-        DQ_TRY_RC(launch_qrcp_colown(A, w, n, n_chains, s));
+        DQ_TRY(launch_qrcp_colown(A, w, n, n_chains, s));
         return formq_assemble(A, L, d, R, w, n, n_chains, s);
     case QrFamily::Cooperative:
-        DQ_TRY_RC(launch_qrcp_coop(A, w, n, n_chains, s));
+        DQ_TRY(launch_qrcp_coop(A, w, n, n_chains, s));
         return formq_assemble(A, L, d, R, w, n, n_chains, s);
     case QrFamily::Streaming:
         if (n <= 64) return to_ldr_streaming<1>(A, L, d, R, w, n, n_chains, s);

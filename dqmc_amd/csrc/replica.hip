@@ -30,7 +30,7 @@ struct dqmc_comm {
     bool rccl = false;
     ncclComm_t nc = nullptr;
     hipStream_t stream = nullptr;            // collectives of the driver (barrier, allreduce); p2p of a round uses the engine's stream
-    double* dbuf = nullptr;                  // device scratch: 8 doubles (send 0..3, recv 4..7)
+    DevPtr<double> dbuf;                     // device scratch: 8 doubles (send 0..3, recv 4..7)
     dqmc_sendrecv_fn fn = nullptr; void* user = nullptr;
     std::vector<int8_t> h_send, h_recv;      // callback transport staging
 };
@@ -74,9 +74,9 @@ static int p2p_host(dqmc_comm* c, const double* send, double* recv, int count, i
         if (c->fn(c->user, send, recv, sizeof(double) * count, partner, tag) != 0) { set_error("replica exchange: the sendrecv callback failed"); return DQMC_EINVAL; }
         return 0;
     }
-    DQ_HIP(hipMemcpyAsync(c->dbuf, send, sizeof(double) * count, hipMemcpyHostToDevice, s));
-    DQ_TRY_RC(p2p(c, c->dbuf, c->dbuf + 4, sizeof(double) * count, partner, tag, s));
-    DQ_HIP(hipMemcpyAsync(recv, c->dbuf + 4, sizeof(double) * count, hipMemcpyDeviceToHost, s));
+    DQ_HIP(hipMemcpyAsync(c->dbuf.get(), send, sizeof(double) * count, hipMemcpyHostToDevice, s));
+    DQ_TRY(p2p(c, c->dbuf.get(), c->dbuf.get() + 4, sizeof(double) * count, partner, tag, s));
+    DQ_HIP(hipMemcpyAsync(recv, c->dbuf.get() + 4, sizeof(double) * count, hipMemcpyDeviceToHost, s));
     DQ_HIP(hipStreamSynchronize(s));
     return 0;
 }
@@ -135,7 +135,7 @@ static int launch_exchange(bool restore, int8_t* fields, int8_t* saved, const in
 // (the pair with the smallest index still open always has both ends at it).
 static int exchange_round(dqmc_engine* e, dqmc_comm* c, int exchange_attempt, const double* u, dqmc_exchange_result* res) {
     EngineFieldsView v;
-    DQ_TRY_RC(engine_fields_view(e, &v));
+    DQ_TRY(engine_fields_view(e, &v));
     const int C = v.n_chains;
     if (c && c->rccl && c->device != v.device) { set_error("replica exchange: the communicator and the engine are on different devices"); return DQMC_EINVAL; }
     const int rank = c ? c->rank : 0, world = (c ? c->world : 1) * C;
@@ -162,7 +162,7 @@ static int exchange_round(dqmc_engine* e, dqmc_comm* c, int exchange_attempt, co
     if (c && c->rccl && !c->dbuf) { set_error("replica exchange: communicator has no device scratch"); return DQMC_EINVAL; }
     const size_t bytes = (size_t)v.nt * v.n;
     int8_t* saved = nullptr; int8_t* recv = nullptr; int* tab = nullptr;
-    DQ_TRY_RC(engine_exchange_scratch(e, &saved, &recv, &tab));
+    DQ_TRY(engine_exchange_scratch(e, &saved, &recv, &tab));
     hipStream_t s = v.stream;
     // the device tables are uploaded from `desc` on the engine's stream; every return waits for the stream first, so no copy is still
     // reading `desc` when it goes away
@@ -178,15 +178,15 @@ static int exchange_round(dqmc_engine* e, dqmc_comm* c, int exchange_attempt, co
         if (rc != 0 && c->rccl && c->nc) { (void)ncclCommAbort(c->nc); c->nc = nullptr; }
         return rc;
     };
-    DQ_TRY_RC(dqmc_sync(e));                                                       // the sweep that precedes the round has finished
+    DQ_TRY(dqmc_sync(e));                                                       // the sweep that precedes the round has finished
     // --- the fields of the boundary partners (MPI_Sendrecv tag 0, source/update.cpp:59-69) ---
     for (const Boundary& b : edge)
-        DQ_TRY_RC(wire(p2p(c, v.fields + (size_t)b.chain * bytes, recv + (size_t)b.slot * bytes, bytes, b.partner_rank, 0, s)));
+        DQ_TRY(wire(p2p(c, v.fields + (size_t)b.chain * bytes, recv + (size_t)b.slot * bytes, bytes, b.partner_rank, 0, s)));
     // --- S_r({s}_r), then the trial state on the partner's fields: S_r({s}_partner) (:72-81) ---
     std::vector<double> S((size_t)C, 0.0), Sp((size_t)C, 0.0);
     local(dqmc_global_action(e, S.data()));                                        // synchronises: the received fields have landed
     DQ_HIP(hipMemcpyAsync(tab, desc.data(), sizeof(int) * 2 * C, hipMemcpyHostToDevice, s));
-    DQ_TRY_RC(launch_exchange(false, v.fields, saved, recv, tab, bytes, C, s));
+    DQ_TRY(launch_exchange(false, v.fields, saved, recv, tab, bytes, C, s));
     if (local(engine_fields_changed(e)) == 0 && local(dqmc_init(e)) == 0) local(dqmc_global_action(e, Sp.data()));
     for (int k = 0; k < C; ++k) {
         res[k].S = S[k]; res[k].S_prime = Sp[k];
@@ -199,7 +199,7 @@ static int exchange_round(dqmc_engine* e, dqmc_comm* c, int exchange_attempt, co
         dqmc_exchange_result& r = res[b.chain];
         const double mine[3] = {r.S_prime, r.S, lrc ? 1.0 : 0.0};
         double theirs[3] = {0.0, 0.0, 0.0};
-        DQ_TRY_RC(wire(p2p_host(c, mine, theirs, 3, b.partner_rank, 1, s)));
+        DQ_TRY(wire(p2p_host(c, mine, theirs, 3, b.partner_rank, 1, s)));
         r.S_prime_partner = theirs[0]; r.S_partner = theirs[1];
         if (theirs[2] != 0.0) { broken[b.chain] = 1; partner_failed = true; }
     }
@@ -216,7 +216,7 @@ static int exchange_round(dqmc_engine* e, dqmc_comm* c, int exchange_attempt, co
         dqmc_exchange_result& r = res[b.chain];
         const double flag_mine = r.decider && r.accepted ? 1.0 : 0.0;
         double flag_theirs = 0.0;
-        DQ_TRY_RC(wire(p2p_host(c, &flag_mine, &flag_theirs, 1, b.partner_rank, 3, s)));
+        DQ_TRY(wire(p2p_host(c, &flag_mine, &flag_theirs, 1, b.partner_rank, 3, s)));
         if (!r.decider) r.accepted = (!broken[b.chain] && flag_theirs != 0.0) ? 1 : 0;
     }
     // --- rejected: restore the own fields and re-initialise (:108-115); one init covers every chain ---
@@ -227,9 +227,9 @@ static int exchange_round(dqmc_engine* e, dqmc_comm* c, int exchange_attempt, co
     }
     if (any_rejected) {
         DQ_HIP(hipMemcpyAsync(tab + C, desc.data() + C, sizeof(int) * C, hipMemcpyHostToDevice, s));
-        DQ_TRY_RC(launch_exchange(true, v.fields, saved, recv, tab, bytes, C, s));
-        DQ_TRY_RC(engine_fields_changed(e));
-        DQ_TRY_RC(dqmc_init(e));
+        DQ_TRY(launch_exchange(true, v.fields, saved, recv, tab, bytes, C, s));
+        DQ_TRY(engine_fields_changed(e));
+        DQ_TRY(dqmc_init(e));
     }
     if (lrc != 0) { set_error("replica exchange: " + lmsg + " (round treated as rejected on both ranks, own fields restored)"); return lrc; }
     if (partner_failed) { set_error("replica exchange: the partner rank reported a failure during the round (treated as rejected, own fields restored)"); return DQMC_ENUMERIC; }
@@ -246,7 +246,7 @@ int dqmc_partner_rank(int rank, int world_size, int exchange_attempt) {       //
 
 int dqmc_comm_unique_id(void* id) {
     if (!id) { set_error("null id"); return DQMC_EINVAL; }
-    DQ_TRY_RC(have_device());
+    DQ_TRY(have_device());
     static_assert(sizeof(ncclUniqueId) == DQMC_UNIQUE_ID_BYTES, "unique id size");
     ncclUniqueId u;
     DQ_NCCL(ncclGetUniqueId(&u));
@@ -256,7 +256,7 @@ int dqmc_comm_unique_id(void* id) {
 
 int dqmc_comm_create_rccl(dqmc_comm** out, const void* id, int world_size, int rank, int device) {
     if (!out || !id || world_size < 1 || rank < 0 || rank >= world_size) { set_error("bad argument"); return DQMC_EINVAL; }
-    DQ_TRY_RC(have_device());
+    DQ_TRY(have_device());
     int count = 0; DQ_HIP(hipGetDeviceCount(&count));
     if (device < 0 || device >= count) { set_error("device ordinal out of range"); return DQMC_EINVAL; }
     DQ_HIP(hipSetDevice(device));
@@ -266,7 +266,7 @@ int dqmc_comm_create_rccl(dqmc_comm** out, const void* id, int world_size, int r
     ncclUniqueId u; std::memcpy(&u, id, sizeof(u));
     ncclResult_t r = ncclCommInitRank(&c->nc, world_size, u, rank);
     if (r != ncclSuccess) { set_error(std::string("ncclCommInitRank: ") + ncclGetErrorString(r)); delete c; return DQMC_ENODEVICE; }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc(&c->dbuf, sizeof(double) * 8) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || dev_alloc(c->dbuf, 8) != 0) {
         set_error("dqmc_comm_create_rccl: stream / scratch allocation failed"); dqmc_comm_destroy(c); return DQMC_ENODEVICE;
     }
     *out = c; return 0;
@@ -283,10 +283,9 @@ int dqmc_comm_create_callbacks(dqmc_comm** out, int world_size, int rank, dqmc_s
 void dqmc_comm_destroy(dqmc_comm* c) {
     if (!c) return;
     if (c->device >= 0) (void)hipSetDevice(c->device);
-    if (c->dbuf) (void)hipFree(c->dbuf);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     if (c->nc) (void)ncclCommDestroy(c->nc);
-    delete c;
+    delete c;                                // frees dbuf
 }
 int dqmc_comm_rank(dqmc_comm* c) { return c ? c->rank : -1; }
 int dqmc_comm_world_size(dqmc_comm* c) { return c ? c->world : 0; }
@@ -298,9 +297,9 @@ int dqmc_comm_allreduce_sum(dqmc_comm* c, double* x, int count) {
     if (c->rccl && !c->nc) { set_error("communicator aborted after an earlier wire error: destroy it and create a new one"); return DQMC_EINVAL; }
     if (c->rccl) {
         DQ_HIP(hipSetDevice(c->device));
-        DQ_HIP(hipMemcpyAsync(c->dbuf, x, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-        DQ_NCCL(ncclAllReduce(c->dbuf, c->dbuf + 4, count, ncclDouble, ncclSum, c->nc, c->stream));
-        DQ_HIP(hipMemcpyAsync(x, c->dbuf + 4, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+        DQ_HIP(hipMemcpyAsync(c->dbuf.get(), x, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+        DQ_NCCL(ncclAllReduce(c->dbuf.get(), c->dbuf.get() + 4, count, ncclDouble, ncclSum, c->nc, c->stream));
+        DQ_HIP(hipMemcpyAsync(x, c->dbuf.get() + 4, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
         DQ_HIP(hipStreamSynchronize(c->stream));
         return 0;
     }
@@ -331,29 +330,25 @@ int dqmc_comm_selftest(dqmc_comm* c) {
     if (!c->nc) { set_error("communicator aborted after an earlier wire error: destroy it and create a new one"); return DQMC_EINVAL; }
     DQ_HIP(hipSetDevice(c->device));
     const size_t bytes = 4096;
-    int8_t* a = nullptr; int8_t* b = nullptr;
-    DQ_HIP(hipMalloc(&a, bytes)); DQ_HIP(hipMalloc(&b, bytes));
+    DevPtr<int8_t> a, b;
+    DQ_TRY(dev_alloc(a, bytes)); DQ_TRY(dev_alloc(b, bytes));
     std::vector<int8_t> h(bytes), g(bytes, 0);
     for (size_t k = 0; k < bytes; ++k) h[k] = (int8_t)((k * 7 + c->rank) & 3);
-    int rc = 0;
-    do {
-        if (hipMemcpyAsync(a, h.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipMemsetAsync(b, 0, bytes, c->stream) != hipSuccess) { set_error("comm_selftest: copy failed"); rc = DQMC_ENODEVICE; break; }
-        rc = p2p(c, a, b, bytes, c->rank, 0, c->stream); if (rc) break;
-        if (hipMemcpyAsync(g.data(), b, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { set_error("comm_selftest: copy back failed"); rc = DQMC_ENODEVICE; break; }
-        if (std::memcmp(h.data(), g.data(), bytes) != 0) { set_error("comm_selftest: loop-back data mismatch"); rc = DQMC_ENUMERIC; break; }
-        const double x[2] = {1.5 + c->rank, -2.0}; double y[2] = {0.0, 0.0};
-        rc = p2p_host(c, x, y, 2, c->rank, 1, c->stream); if (rc) break;
-        if (y[0] != x[0] || y[1] != x[1]) { set_error("comm_selftest: loop-back of two doubles mismatch"); rc = DQMC_ENUMERIC; break; }
-        double z[2] = {1.0, (double)c->rank};
-        if (hipMemcpyAsync(c->dbuf, z, sizeof(z), hipMemcpyHostToDevice, c->stream) != hipSuccess) { set_error("comm_selftest: copy failed"); rc = DQMC_ENODEVICE; break; }
-        ncclResult_t r = ncclAllReduce(c->dbuf, c->dbuf + 4, 2, ncclDouble, ncclSum, c->nc, c->stream);
-        if (r != ncclSuccess) { set_error(std::string("comm_selftest: ncclAllReduce: ") + ncclGetErrorString(r)); rc = DQMC_ENODEVICE; break; }
-        if (hipMemcpyAsync(z, c->dbuf + 4, sizeof(z), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { set_error("comm_selftest: copy back failed"); rc = DQMC_ENODEVICE; break; }
-        const double want1 = 0.5 * c->world * (c->world - 1);
-        if (z[0] != (double)c->world || z[1] != want1) { set_error("comm_selftest: all-reduce result mismatch"); rc = DQMC_ENUMERIC; break; }
-    } while (false);
-    (void)hipFree(a); (void)hipFree(b);
-    return rc;
+    if (hipMemcpyAsync(a.get(), h.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipMemsetAsync(b.get(), 0, bytes, c->stream) != hipSuccess) { set_error("comm_selftest: copy failed"); return DQMC_ENODEVICE; }
+    DQ_TRY(p2p(c, a.get(), b.get(), bytes, c->rank, 0, c->stream));
+    if (hipMemcpyAsync(g.data(), b.get(), bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { set_error("comm_selftest: copy back failed"); return DQMC_ENODEVICE; }
+    if (std::memcmp(h.data(), g.data(), bytes) != 0) { set_error("comm_selftest: loop-back data mismatch"); return DQMC_ENUMERIC; }
+    const double x[2] = {1.5 + c->rank, -2.0}; double y[2] = {0.0, 0.0};
+    DQ_TRY(p2p_host(c, x, y, 2, c->rank, 1, c->stream));
+    if (y[0] != x[0] || y[1] != x[1]) { set_error("comm_selftest: loop-back of two doubles mismatch"); return DQMC_ENUMERIC; }
+    double z[2] = {1.0, (double)c->rank};
+    if (hipMemcpyAsync(c->dbuf.get(), z, sizeof(z), hipMemcpyHostToDevice, c->stream) != hipSuccess) { set_error("comm_selftest: copy failed"); return DQMC_ENODEVICE; }
+    ncclResult_t r = ncclAllReduce(c->dbuf.get(), c->dbuf.get() + 4, 2, ncclDouble, ncclSum, c->nc, c->stream);
+    if (r != ncclSuccess) { set_error(std::string("comm_selftest: ncclAllReduce: ") + ncclGetErrorString(r)); return DQMC_ENODEVICE; }
+    if (hipMemcpyAsync(z, c->dbuf.get() + 4, sizeof(z), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { set_error("comm_selftest: copy back failed"); return DQMC_ENODEVICE; }
+    const double want1 = 0.5 * c->world * (c->world - 1);
+    if (z[0] != (double)c->world || z[1] != want1) { set_error("comm_selftest: all-reduce result mismatch"); return DQMC_ENUMERIC; }
+    return 0;
 }
 int dqmc_comm_barrier(dqmc_comm* c) { double z = 0.0; return dqmc_comm_allreduce_sum(c, &z, 1); }
 
@@ -362,7 +357,7 @@ int dqmc_replica_exchange_round(dqmc_engine* e, dqmc_comm* c, int exchange_attem
     std::memset(res, 0, sizeof(*res));
     res->partner = -1;
     EngineFieldsView v;
-    DQ_TRY_RC(engine_fields_view(e, &v));
+    DQ_TRY(engine_fields_view(e, &v));
     if (v.n_chains != 1) { set_error("replica exchange: one chain per rank (a batched engine holds several: dqmc_replica_exchange_batch)"); return DQMC_EINVAL; }
     return exchange_round(e, c, exchange_attempt, &u, res);
 }
@@ -376,7 +371,7 @@ int dqmc_replica_exchange_batch(dqmc_engine* e, dqmc_comm* c, int exchange_attem
     EngineFieldsView v{};
     if (!e || !res) bad = "null engine or result array";
     else {
-        DQ_TRY_RC(engine_fields_view(e, &v));
+        DQ_TRY(engine_fields_view(e, &v));
         for (int k = 0; k < v.n_chains; ++k) { std::memset(res + k, 0, sizeof(*res)); res[k].partner = -1; }
         if (!u) bad = "null uniform array u";
         else if (!c && v.n_chains == 1) bad = "a single chain without a communicator has nobody to swap with";
@@ -385,7 +380,7 @@ int dqmc_replica_exchange_batch(dqmc_engine* e, dqmc_comm* c, int exchange_attem
     if (c && c->world > 1) {
         const double C = bad.empty() ? v.n_chains : -1.0, b = bad.empty() ? (double)v.nt * v.n : 0.0;
         double x[4] = {C, C * C, b, b * b};
-        DQ_TRY_RC(dqmc_comm_allreduce_sum(c, x, 4));
+        DQ_TRY(dqmc_comm_allreduce_sum(c, x, 4));
         const double R = c->world;
         if (bad.empty() && (x[0] * x[0] != R * x[1] || x[2] * x[2] != R * x[3]))
             bad = "every rank must hold the same number of chains of the same size (another rank differs, or refused its arguments)";
