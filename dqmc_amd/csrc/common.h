@@ -133,12 +133,11 @@ struct QrWork {
     unsigned long long* sync = nullptr; long sync_stride = 0;   // cooperative QRCP: granule records, >= qrcp_coop_sync_granules(n) per chain
     int* abort_words = nullptr;                                 // cooperative QRCP: one word per chain
     int* info = nullptr;                                        // status block: |= DQ_STATUS_COOP_QR when a cooperative factorisation gave up waiting
-    double* pw = nullptr; long pw_stride = 0;                   // panel-pivoted QR (qr_panel.hip): sketch, clean reflector panel, T; >= qr_panel_work_doubles(n) per chain
+    double* pw = nullptr; long pw_stride = 0;                   // panel-pivoted QR (qr_panel.hip): sketch, clean reflector panels, T, Q accumulator; >= qr_panel_work_doubles(n) per chain
     int* pivpos = nullptr; long pivpos_stride = 0;              // panel-pivoted QR: pivot position of every column (-1 = live), n per chain
 };
 long qr_panel_work_doubles(int n);
-int launch_qr_panel_formq(QrWork w, Mat L, int n, int n_chains, hipStream_t s);   // explicit Q of that factorisation from its compact-WY factors (left in w.pw)
-int launch_qr_panel(Mat A, QrWork w, int n, int n_chains, hipStream_t s);   // qr_panel.hip: A -> reflectors / R0 in place, tau, jpvt (same format as the QRCP kernels)
+int launch_qr_panel(Mat A, Mat L, QrWork w, int n, int n_chains, hipStream_t s);   // qr_panel.hip: A -> reflectors / R0 in place, tau, jpvt (same format as the QRCP kernels); L = the explicit Q
 long qrcp_coop_sync_granules(int n);        // granules of cooperative-QRCP workspace per chain
 int qrcp_coop_workgroups(int n, int n_chains);
 // the factorisation to_LDR runs on (chosen by pick_qr, engine.hip): panel-pivoted blocked QR (qr_panel.hip), column-owner QRCP on one

@@ -103,25 +103,33 @@ struct LdrRef {                 // a batched LDR triple in HBM
     Mat L; Vec d; Mat R;
     int* jpvt = nullptr;        // [C][n] pivot order storage of this triple (may be null)
     bool* tri = nullptr;        // host flag: R is the permuted-triangular factor of ONE to_LDR (jpvt valid)
+    Mat X{nullptr, 0};          // cache slot for R^-1 diag(1 / max(d, 1)) of this triple (may be null: no slot)
+    bool* xok = nullptr;        // host flag: X holds that matrix for the current d and R
+    void touch() const { if (xok) *xok = false; }                // d or R is about to be rewritten
 };
-// k batched LDR triples: L, R [k][C][nn], d and the pivot order of R [k][C][n], and the host flag `tri` of each triple
+// k batched LDR triples: L, R [k][C][nn], d and the pivot order of R [k][C][n], and the host flag `tri` of each triple.
+// with_x: every triple also gets a cache slot X [k][C][nn] for R^-1 diag(1 / max(d, 1)) and its host flag `xok` (Ctx::r_inverse_scaled
+// fills and reuses it); the slots are half as large again as L and R together, so only the engine's stack asks for them.
 struct LdrStore {
     int n = 0, C = 0;
-    DevPtr<double> L, d, R;
+    DevPtr<double> L, d, R, X;
     DevPtr<int> jpvt;
-    std::unique_ptr<bool[]> tri;               // an array on the heap: LdrRef::tri stays valid when the store is moved
-    int alloc(int k, int n_, int C_) {
+    std::unique_ptr<bool[]> tri, xok;          // arrays on the heap: LdrRef::tri / xok stay valid when the store is moved
+    int alloc(int k, int n_, int C_, bool with_x = false) {
         n = n_; C = C_;
         const size_t nn = (size_t)n * n;
         DQ_TRY(dev_alloc(L, (size_t)k * C * nn)); DQ_TRY(dev_alloc(d, (size_t)k * C * n));
         DQ_TRY(dev_alloc(R, (size_t)k * C * nn)); DQ_TRY(dev_alloc(jpvt, (size_t)k * C * n));
-        tri.reset(new bool[k]());
+        if (with_x) DQ_TRY(dev_alloc(X, (size_t)k * C * nn));
+        tri.reset(new bool[k]()); xok.reset(new bool[k]());
         return 0;
     }
     LdrRef at(int i) const {
         const long nn = (long)n * n;
-        return LdrRef{Mat{L.get() + (long)i * C * nn, nn}, Vec{d.get() + (long)i * C * n, (long)n}, Mat{R.get() + (long)i * C * nn, nn},
-                      jpvt.get() + (long)i * C * n, &tri[i]};
+        LdrRef f{Mat{L.get() + (long)i * C * nn, nn}, Vec{d.get() + (long)i * C * n, (long)n}, Mat{R.get() + (long)i * C * nn, nn},
+                 jpvt.get() + (long)i * C * n, &tri[i]};
+        if (X) { f.X = Mat{X.get() + (long)i * C * nn, nn}; f.xok = &xok[i]; }
+        return f;
     }
 };
 
@@ -179,17 +187,26 @@ struct Ctx {
         w.sync = qsync.get(); w.sync_stride = qrcp_coop_sync_granules(n); w.abort_words = qabort.get(); w.info = info();
         w.pw = qpw.get(); w.pw_stride = qr_panel_work_doubles(n); w.pivpos = qpivpos.get(); w.pivpos_stride = n;
         if (out.tri) *out.tri = keep;
+        out.touch();
         return launch_to_ldr(plan.qr, A, out.L, out.d, out.R, w, n, C, stream);
     }
-    // X = F.R^-1 diag(dinv): permuted triangular solve when F.R is a single QR factor, LU otherwise
-    int r_inverse_scaled(LdrRef F, CVec dinv, Mat X, Mat lu_scratch) {
+    // X = F.R^-1 diag(dinv), dinv = 1 / max(F.d, 1): permuted triangular solve when F.R is a single QR factor, LU otherwise.
+    // *Xout is the matrix that holds X: the triple's own slot when it has one (computed once per (d, R): a valid slot costs no
+    // launch), `scratch` otherwise.  X is only read afterwards.
+    int r_inverse_scaled(LdrRef F, CVec dinv, Mat scratch, Mat lu_scratch, Mat* Xout) {
+        const Mat X = F.X.p ? F.X : scratch;
+        *Xout = X;
+        if (F.xok && *F.xok) return 0;
         if (F.tri && *F.tri && F.jpvt) {
-            if (plan.rinv == KernelPlan::Rinv::Blocked) return launch_tri_solve(F.R, F.jpvt, n, X, dinv, trinv.get(), 16L * (n + 16), n, C, stream);
-            return launch_lu_solve(F.R, F.jpvt, n, X, dinv, 2, n, C, stream);
+            if (plan.rinv == KernelPlan::Rinv::Blocked) DQ_TRY(launch_tri_solve(F.R, F.jpvt, n, X, dinv, trinv.get(), 16L * (n + 16), n, C, stream));
+            else DQ_TRY(launch_lu_solve(F.R, F.jpvt, n, X, dinv, 2, n, C, stream));
+        } else {
+            DQ_TRY(launch_copy(F.R, lu_scratch, nn, C, stream));
+            DQ_TRY(launch_lu_blocked(lu_scratch, lperm(), n, rowpos(), n, nullptr, 0, info(), n, C, stream));
+            DQ_TRY(launch_lu_solve(lu_scratch, lperm(), n, X, dinv, 1, n, C, stream));
         }
-        DQ_TRY(launch_copy(F.R, lu_scratch, nn, C, stream));
-        DQ_TRY(launch_lu_blocked(lu_scratch, lperm(), n, rowpos(), n, nullptr, 0, info(), n, C, stream));
-        return launch_lu_solve(lu_scratch, lperm(), n, X, dinv, 1, n, C, stream);
+        if (F.xok) *F.xok = true;
+        return 0;
     }
     // stablelinalg::mat_mul_ldr (source/stablelinalg.cpp:69-79): out = M * F   (uses T0,T1)
     int mat_mul_ldr(CMat M, LdrRef F, LdrRef out) {
@@ -197,12 +214,14 @@ struct Ctx {
         LdrRef q{out.L, out.d, T(1)};
         DQ_TRY(to_ldr(T(0), q));
         if (out.tri) *out.tri = false;                                   // R becomes a product
+        out.touch();
         return gemm(T(1), F.R, out.R);                                   // r * R
     }
     // stablelinalg::ldr_mul_mat (source/stablelinalg.cpp:57-67): out = F * M   (uses T0,T1)
     int ldr_mul_mat(LdrRef F, CMat M, LdrRef out) {
         DQ_TRY(gemm(F.R, M, T(0), CVec(F.d)));                            // diag(d) (R M)
         LdrRef q{T(1), out.d, out.R, out.jpvt, out.tri};                  // R = the QR's own factor
+        q.xok = out.xok;                                                 // to_ldr marks out's cached X stale
         DQ_TRY(to_ldr(T(0), q));
         return gemm(F.L, T(1), out.L);                                   // L * q
     }
@@ -212,6 +231,7 @@ struct Ctx {
         LdrRef q{T(1), out.d, T(2)};
         DQ_TRY(to_ldr(T(0), q));
         if (out.tri) *out.tri = false;
+        out.touch();
         DQ_TRY(gemm(F1.L, T(1), out.L));
         return gemm(T(2), F2.R, out.R);
     }
@@ -231,33 +251,34 @@ struct Ctx {
     // log|det M| comes from that same factorisation (det M^T = det M).
     int inv_I_plus_ldr(LdrRef F, Mat G, double* logdet /*device, C*/) {
         DQ_TRY(launch_split_d(F.d, V(0), V(1), logdet, n, C, stream));                 // V0 = 1/Dl, V1 = Ds, logdet = sum log Dl
-        DQ_TRY(r_inverse_scaled(F, V(0), T(1), T(0)));                                  // X = R^-1 diag(1/Dl)
-        DQ_TRY(launch_add_scaled_cols(T(1), F.L, V(1), T(2), n, C, stream));            // M = X + L diag(Ds)
+        Mat X; DQ_TRY(r_inverse_scaled(F, V(0), T(1), T(0), &X));                       // X = R^-1 diag(1/Dl)
+        DQ_TRY(launch_add_scaled_cols(X, F.L, V(1), T(2), n, C, stream));               // M = X + L diag(Ds)
         DQ_TRY(launch_transpose_scale(T(2), T(3), CVec(), n, C, stream));               // M^T
-        DQ_TRY(launch_transpose_scale(T(1), T(4), CVec(), n, C, stream));               // X^T
+        DQ_TRY(launch_transpose_scale(X, T(4), CVec(), n, C, stream));                  // X^T
         Mat Y; DQ_TRY(solve(T(3), T(4), T(0), logdet, &Y));                             // G^T; logdet += log|det M|
         return launch_transpose_scale(Y, G, CVec(), n, C, stream);
     }
     // stablelinalg::inv_I_plus_ldr_mul_ldr (source/stablelinalg.cpp:128-158)   (uses T0..T3, V0..V3)
-    int inv_I_plus_ldr_mul_ldr(LdrRef F1, LdrRef F2, Mat G) {
+    // GT (optional) receives G^T as well, from the product that writes G
+    int inv_I_plus_ldr_mul_ldr(LdrRef F1, LdrRef F2, Mat G, Mat GT = Mat{nullptr, 0}) {
         DQ_TRY(launch_split_d2(F1.d, V(0), V(1), F2.d, V(2), V(3), n, C, stream));     // 1/D1l, D1s | 1/D2l, D2s
-        DQ_TRY(r_inverse_scaled(F2, V(2), T(1), T(0)));                                 // X = R2^-1 diag(1/D2l)
-        DQ_TRY(gemm(F1.L, T(1), T(2), V(0), CVec(), CVec(), 1));                        // TermA = diag(1/D1l) L1^T X
+        Mat X; DQ_TRY(r_inverse_scaled(F2, V(2), T(1), T(0), &X));                      // X = R2^-1 diag(1/D2l)
+        DQ_TRY(gemm(F1.L, X, T(2), V(0), CVec(), CVec(), 1));                           // TermA = diag(1/D1l) L1^T X
         DQ_TRY(gemm(F1.R, F2.L, T(2), V(1), CVec(), V(3), 0, 1));                       // M = TermA + diag(D1s) R1 L2 diag(D2s)
         DQ_TRY(launch_transpose_scale(F1.L, T(3), V(0), n, C, stream));                 // RHS = diag(1/D1l) L1^T
         Mat Y; DQ_TRY(solve(T(2), T(3), T(0), nullptr, &Y));                            // Y = M^-1 RHS
-        return gemm(T(1), Y, G);                                                        // G = X Y
+        return gemm(X, Y, G, CVec(), CVec(), CVec(), 0, 0, GT);                         // G = X Y
     }
     // stablelinalg::inv_invldr_plus_ldr (source/stablelinalg.cpp:160-190): G = [F1^-1 + F2]^-1 (negated on request)   (uses T0..T3, V0..V3)
     int inv_invldr_plus_ldr(LdrRef F1, LdrRef F2, Mat G, bool negate) {
         DQ_TRY(launch_split_d(F1.d, V(0), V(1), nullptr, n, C, stream));               // 1/D1l, D1s
         DQ_TRY(launch_split_d(F2.d, V(2), V(3), nullptr, n, C, stream));               // 1/D2l, D2s
-        DQ_TRY(r_inverse_scaled(F2, V(2), T(1), T(0)));                                 // X = R2^-1 diag(1/D2l)
-        DQ_TRY(gemm(F1.L, T(1), T(2), V(0), CVec(), CVec(), 1));                        // TermA = diag(1/D1l) L1^T X
+        Mat X; DQ_TRY(r_inverse_scaled(F2, V(2), T(1), T(0), &X));                      // X = R2^-1 diag(1/D2l)
+        DQ_TRY(gemm(F1.L, X, T(2), V(0), CVec(), CVec(), 1));                           // TermA = diag(1/D1l) L1^T X
         DQ_TRY(gemm(F1.R, F2.L, T(2), V(1), CVec(), V(3), 0, 1));                       // M = TermA + diag(D1s) R1 L2 diag(D2s)
         DQ_TRY(launch_scale_rows(F1.R, V(1), T(3), n, C, stream));                      // RHS = diag(D1s) R1
         Mat Y; DQ_TRY(solve(T(2), T(3), T(0), nullptr, &Y));                            // Y = M^-1 RHS
-        DQ_TRY(gemm(T(1), Y, G));                                                       // G = X Y
+        DQ_TRY(gemm(X, Y, G));                                                          // G = X Y
         if (negate) DQ_TRY(launch_axpb_identity(G, G, -1.0, 0.0, n, C, stream));
         return 0;
     }
@@ -311,7 +332,8 @@ struct Engine {
     DevPtr<int8_t> fields;                                       // [C][nt][n]
     DevPtr<double> expv, invexpv;                                // [C][nt][n]
     DevPtr<UpdateTables> tabs; DevPtr<double> tab8;              // [C], [C][8]
-    bool gt_valid = false;                                       // GT == G^T right now (set by the wraps, cleared by everything else that writes G)
+    bool gt_valid = false;                                       // GT == G^T right now (set by the wraps and the backward stabilisations, cleared by everything else that writes G)
+    bool gt_check = false; long long gt_checks = 0; DevPtr<double> gt_err;   // dqmc_debug_gt_check: max|GT - G^T| [C] over the stabilisations that left GT valid
     DevPtr<double> G, Gtmp, GT;                                  // [C][nn]; GT: transposed copy for the local-update walk
     DevPtr<double> pg_eye, pg_ones;                              // identity [nn] and ones [n]: operands of the first piggybacked B-bar factor of a block (single chain)
     DevPtr<double> bb0, bb1;                                     // Bbar ping-pong
@@ -383,7 +405,8 @@ struct Engine {
         DQ_TRY(dev_alloc(tabs, C)); DQ_TRY(dev_alloc(tab8, (size_t)C * 8));
         if (C == 1) { DQ_TRY(dev_alloc(pg_eye, nn)); DQ_TRY(dev_alloc(pg_ones, (size_t)n)); DQ_TRY(launch_set_identity(Mat{pg_eye.get(), nn}, n, 1, s)); const std::vector<double> one_h((size_t)n, 1.0); DQ_HIP(hipMemcpy(pg_ones.get(), one_h.data(), sizeof(double) * n, hipMemcpyHostToDevice)); }
         DQ_TRY(dev_alloc(G, C * nn)); DQ_TRY(dev_alloc(Gtmp, C * nn)); DQ_TRY(dev_alloc(GT, C * nn)); DQ_TRY(dev_alloc(bb0, C * nn)); DQ_TRY(dev_alloc(bb1, C * nn));
-        DQ_TRY(stack.alloc(n_stack, n, C)); DQ_TRY(spare.alloc(1, n, C));
+        // X slots for the stack of the few-chain engines (the latency-bound ones, same limit as the panel QR family): n_stack C nn doubles
+        DQ_TRY(stack.alloc(n_stack, n, C, C <= 8)); DQ_TRY(spare.alloc(1, n, C));
         DQ_TRY(dev_alloc(logdet, C));
         DQ_TRY(dev_alloc(rs_perm, (size_t)C * nt * n)); DQ_TRY(dev_alloc(rs_k, (size_t)C * nt * n)); DQ_TRY(dev_alloc(rs_u, (size_t)C * nt * n));
         DQ_TRY(dev_alloc(Upanel, (size_t)C * UPDATE_KD * n)); DQ_TRY(dev_alloc(Wpanel, (size_t)C * UPDATE_KD * n)); DQ_TRY(dev_alloc(Cpanel, (size_t)C * UPDATE_KD * UPDATE_KD));
@@ -527,7 +550,7 @@ struct Engine {
         DQ_TRY(launch_copy(own.R, last.R, nn, 1, s));
         DQ_HIP(hipMemcpyAsync(last.d.p, own.d.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
         DQ_HIP(hipMemcpyAsync(last.jpvt, own.jpvt, sizeof(int) * n, hipMemcpyDeviceToDevice, s));
-        *last.tri = true;
+        *last.tri = true; last.touch();
         for (int i = S - 2; i >= 0; --i) DQ_TRY(ctx.ldr_mul_ldr(stack.at(i + 1), ib.f.at(i), stack.at(i)));
         stack_valid = true;
         gt_valid = false;
@@ -686,7 +709,15 @@ struct Engine {
                 else DQ_TRY(ctx.ldr_mul_mat(stack.at(is + 1), bb, stack.at(is)));
                 gt_valid = false;
                 if (l == 0) DQ_TRY(ctx.inv_I_plus_ldr(stack.at(is), mG(), logdet.get()));                // stabilize_GF_backward :203-215
-                else DQ_TRY(ctx.inv_I_plus_ldr_mul_ldr(stack.at(is - 1), stack.at(is), mG()));
+                else {                                                                       // the next launch is a local update: G = X Y writes GT as well
+                    DQ_TRY(ctx.inv_I_plus_ldr_mul_ldr(stack.at(is - 1), stack.at(is), mG(), use_gt() ? Mat{GT.get(), nn} : Mat{nullptr, 0}));
+                    gt_valid = use_gt();
+                    if (gt_check && gt_valid) {                                              // diagnostic: GT against a transpose of G
+                        DQ_TRY(launch_transpose_scale(mG(), ctx.T(0), CVec(), n, C, s));
+                        DQ_TRY(launch_max_abs_diff(CMat(GT.get(), nn), ctx.T(0), gt_err.get(), 1, n, C, s));
+                        ++gt_checks;
+                    }
+                }
                 DQ_TRY(launch_max_abs_diff(CMat(Gtmp.get(), nn), mG(), err.get() + n_err, n_stack, n, C, s));
                 ++n_err;
             }
@@ -1167,6 +1198,15 @@ int dqmc_debug_snapshot(dqmc_engine* h, double* wrap_err, int* accepted, unsigne
     if (accepted) DQ_HIP(hipMemcpy(accepted, e.acc.get(), sizeof(int) * e.nt, hipMemcpyDeviceToHost));
     if (sync_words) DQ_HIP(hipMemcpy(sync_words, e.slice_sync.get(), sizeof(unsigned int) * 80, hipMemcpyDeviceToHost));
     if (slice_epoch) *slice_epoch = e.slice_epoch;
+    return 0;
+}
+int dqmc_debug_gt_check(dqmc_engine* h, int on, double* max_err, int64_t* n_checks) {
+    ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
+    if (!e.gt_err) { DQ_TRY(dev_alloc(e.gt_err, e.C)); DQ_HIP(hipMemset(e.gt_err.get(), 0, sizeof(double) * e.C)); }
+    if (max_err) DQ_HIP(hipMemcpy(max_err, e.gt_err.get(), sizeof(double) * e.C, hipMemcpyDeviceToHost));
+    if (n_checks) *n_checks = e.gt_checks;
+    DQ_HIP(hipMemset(e.gt_err.get(), 0, sizeof(double) * e.C));
+    e.gt_checks = 0; e.gt_check = on != 0;
     return 0;
 }
 int dqmc_slice_path(dqmc_engine* h) {

@@ -378,8 +378,7 @@ static int formq_assemble(Mat A, Mat L, Vec d, Mat R, const QrWork& w, int n, in
     return launch_assemble_r(A, d, R, w, n, n_chains, s);
 }
 static int to_ldr_panel(Mat A, Mat L, Vec d, Mat R, const QrWork& w, int n, int n_chains, hipStream_t s) {
-    DQ_TRY(launch_qr_panel(A, w, n, n_chains, s));
-    DQ_TRY(launch_qr_panel_formq(w, L, n, n_chains, s));
+    DQ_TRY(launch_qr_panel(A, L, w, n, n_chains, s));               // Q is accumulated beside the trailing updates
     return launch_assemble_r(A, d, R, w, n, n_chains, s);
 }
 // the single-workgroup streaming kernel with NR rows per lane

@@ -16,10 +16,12 @@
 //              and the 15 updates of a step are 16 DPP-FMAs each; ONE fused reduction per step yields the dots, the squared
 //              norm of the pivot column's tail and the entries v_c^T v_j of the compact-WY factor T;
 //   update     A <- (I - V T V^T)^T A on the trailing columns, 16 columns per workgroup, v_mfma_f64_16x16x4_f64;
-//   form Q     Q = H_0 ... H_{n/16-1} from the same compact-WY factors (every panel's clean reflectors and T are kept), MFMA.
+//   form Q     Q^T = H_{n/16-1}^T ... H_0^T I is the same update applied to an n x n buffer that starts as the identity: a second range
+//              of workgroups of every update launch (the Q role, on CUs the launch leaves idle) carries it along, and the 16 rows of
+//              Q^T that factor k completes go straight into L as 16 columns of Q.  No launch of its own.
 //
-// n / 16 panels x (qp_panel_kernel, qp_update_kernel) + qp_formq_kernel: 575 us at n = 256 (qr_colown + formq_blocked: 892), 2.0 ms at
-// n = 576 (qr_coop: 4.26).  Where the time goes, and the forms that were measured and dropped (one persistent launch, a lane pair per
+// n / 16 panels x (qp_panel_kernel, qp_update_kernel) + the explicit-Q launch of the time: 575 us at n = 256 (qr_colown + formq_blocked:
+// 892), 2.0 ms at n = 576 (qr_coop: 4.26).  Where the time goes, and the forms that were measured and dropped (one persistent launch, a lane pair per
 // sketch column, 24 sketch rows, look-ahead selection): DESIGN.md section 5.
 //
 // Randomised panel pivoting (Duersch & Gu 2017; Martinsson, Quintana-Orti, Heavner, van de Geijn 2017).  The numpy statement
@@ -288,7 +290,7 @@ __global__ __launch_bounds__(64 * NW) void qp_panel_kernel(Mat Am, QrWork w, int
     double* __restrict__ A = Am.at(chain);
     double* __restrict__ pw = w.pw + (long)chain * w.pw_stride;
     const double* __restrict__ Y = pw;                         // [QP_SR][n]
-    double* __restrict__ Vp = pw + (long)QP_SR * n + (long)n * k;                 // [n][QP_B] column-major clean copy of THIS panel's reflectors (all panels are kept: qp_formq_kernel)
+    double* __restrict__ Vp = pw + (long)QP_SR * n + (long)n * k;                 // [n][QP_B] column-major clean copy of THIS panel's reflectors
     double* __restrict__ Tm = pw + (long)QP_SR * n + (long)n * n + (long)QP_B * k;   // [QP_B][QP_B] column-major, one per panel
     double* __restrict__ VTp = pw + (long)QP_SR * n + (long)n * n + (long)QP_B * n + (long)n * k;   // the same panel row-major ([n][QP_B]): the operand of V^T A is read along its rows
     int* __restrict__ pivpos = w.pivpos + (long)chain * w.pivpos_stride;
@@ -400,14 +402,98 @@ __global__ __launch_bounds__(64 * NW) void qp_panel_kernel(Mat Am, QrWork w, int
 // A wave keeps its row tiles (tile rt = wave + QP_UW ti, ti < TPW) in registers in the accumulator layout from the first load on: the same
 // registers are the B operand of W = V^T A (k-step s <-> row kk + 4 s of the tile: any partition of k works as long as V is fed the same
 // way), the accumulator of A - V W', and the B operand of the sketch product.
-constexpr int QP_UW = 8;      // waves per workgroup of the update / form-Q kernels (4: 6.7 / 45.9 us at n = 256 against 6.3 / 40.9; 16: 8.3 / 166)
+constexpr int QP_UW = 8;      // waves per workgroup of the update kernel (4: 6.7 us at n = 256 against 6.3; 16: 8.3)
+constexpr int QP_YT = QP_SR / 16;
+
+// The Q role of an update launch: column block cb of Qacc (n x n, column-major like A; it holds rows >= k of H_{k/16-1}^T ... H_0^T I, the
+// identity before the first factor -- formed in registers then, nothing is cleared) gets the factor of panel k exactly as the
+// trailing matrix does, without a pivot test, a sketch or an early exit.  The later factors start below row k + 16, so rows k .. k + 15
+// of Q^T are final: that tile goes transposed into columns k .. k + 15 of L = Q (the 16 lanes of one (kk, r) write 128 contiguous
+// bytes), the tiles below go back to Qacc for the next launch.  Loads first, as in the A role: one cold round.
+template <int TPW>
+__device__ __forceinline__ void qp_q_role(double (&red)[QP_UW][QP_YT * 4][64], double* __restrict__ Qacc, double* __restrict__ L,
+                                          const double* __restrict__ Vp, const double* __restrict__ VTp, const double* __restrict__ Tm,
+                                          int n, int k, int cb) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r16 = lane & 15, kk = lane >> 4;
+    const int col = 16 * cb + r16;
+    double* __restrict__ Qc = Qacc + (long)n * col;
+    const int m_tiles = (n - k) / 16;
+    d4 Qt[TPW]; double v1[TPW][4], v2[TPW][4], tv[4];
+#pragma unroll
+    for (int ti = 0; ti < TPW; ++ti) {
+        const int rt = wave + QP_UW * ti;
+        Qt[ti] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { v1[ti][s] = 0.0; v2[ti][s] = 0.0; }
+        if (rt < m_tiles) {
+            const int r0 = k + 16 * rt;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Qt[ti][r] = Qc[r0 + kk + 4 * r];     // loaded at k = 0 as well (whatever the last factorisation left) and replaced below: a branch here would put a wait between the rounds of loads
+#pragma unroll
+            for (int s = 0; s < 4; ++s) { v1[ti][s] = VTp[(long)QP_B * (r0 + kk + 4 * s) + r16]; v2[ti][s] = Vp[(long)n * (kk + 4 * s) + (r0 + r16)]; }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) tv[s] = Tm[(kk + 4 * s) + QP_B * r16];
+    const bool first = k == 0;                                    // before the first factor the accumulator is the identity: a select, no branch
+#pragma unroll
+    for (int ti = 0; ti < TPW; ++ti)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Qt[ti][r] = first ? ((16 * (wave + QP_UW * ti) + kk + 4 * r == col) ? 1.0 : 0.0) : Qt[ti][r];
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ti = 0; ti < TPW; ++ti) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v1[ti][s], Qt[ti][s], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave][r][lane] = acc[r];
+    __syncthreads();
+    d4 W;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double v = red[0][r][lane];
+#pragma unroll
+        for (int q = 1; q < QP_UW; ++q) v += red[q][r][lane];
+        W[r] = v;
+    }
+    d4 wp = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) wp = __builtin_amdgcn_mfma_f64_16x16x4f64(tv[s], W[s], wp, 0, 0, 0);
+    wp = -wp;
+#pragma unroll
+    for (int ti = 0; ti < TPW; ++ti) {
+        const int rt = wave + QP_UW * ti;
+        if (rt < m_tiles) {
+            const int r0 = k + 16 * rt;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) Qt[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(v2[ti][s], wp[s], Qt[ti], 0, 0, 0);
+            if (rt == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) L[(long)n * (k + kk + 4 * r) + col] = Qt[ti][r];     // Q[col][k + kk + 4 r] = Q^T[k + kk + 4 r][col]
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Qc[r0 + kk + 4 * r] = Qt[ti][r];
+            }
+        }
+    }
+}
+
+// blockIdx.x >= q_first: the workgroup has the Q role on column block blockIdx.x - q_first (uniform per workgroup)
 template <bool UPDATE, int TPW>
-__global__ __launch_bounds__(64 * QP_UW) void qp_update_kernel(Mat Am, QrWork w, int n, int k) {
-    constexpr int YT = QP_SR / 16;
+__global__ __launch_bounds__(64 * QP_UW) void qp_update_kernel(Mat Am, QrWork w, int n, int k, Mat Lm, int q_first) {
+    constexpr int YT = QP_YT;
     __shared__ double red[QP_UW][YT * 4][64];                  // per wave partial tiles (W: 4 registers, Y: 4 YT registers)
     const int chain = blockIdx.y;
-    double* __restrict__ A = Am.at(chain);
     double* __restrict__ pw = w.pw + (long)chain * w.pw_stride;
+    if (UPDATE && (int)blockIdx.x >= q_first) {
+        qp_q_role<TPW>(red, pw + (long)(QP_SR + 2 * n) * n + (long)QP_B * n, Lm.at(chain), pw + (long)QP_SR * n + (long)n * k,
+                       pw + (long)QP_SR * n + (long)n * n + (long)QP_B * n + (long)n * k, pw + (long)QP_SR * n + (long)n * n + (long)QP_B * k, n, k,
+                       (int)blockIdx.x - q_first);
+        return;
+    }
+    double* __restrict__ A = Am.at(chain);
     double* __restrict__ Y = pw;
     const double* __restrict__ Vp = pw + (long)QP_SR * n + (long)n * k;
     const double* __restrict__ Tm = pw + (long)QP_SR * n + (long)n * n + (long)QP_B * k;
@@ -511,123 +597,27 @@ __global__ __launch_bounds__(64 * QP_UW) void qp_update_kernel(Mat Am, QrWork w,
     }
 }
 
-// Q = H_0 H_1 ... H_{n/16 - 1} applied to I, every factor in its compact-WY form I - V_k T_k V_k^T (the clean reflector panels and the
-// T factors the panel kernel left behind): grid.x = n / 16 column blocks of Q, each kept in registers as accumulator tiles (tile rt =
-// wave + QP_UW ti) through all the factors that touch it -- columns 16 cb .. 16 cb + 15 of the identity are unchanged by the panels
-// k > cb (their reflectors start below row 16 k), so block cb applies panels k = cb .. 0 -- two MFMA products and one LDS reduction
-// per factor, the next factor's operands requested while the current one is multiplied.  77 us (formq_blocked_kernel: one column per
-// 16-lane row, reflector by reflector) -> the figure in DESIGN at n = 256.
-template <int TPW>
-__global__ __launch_bounds__(64 * QP_UW) void qp_formq_kernel(QrWork w, Mat Lm, int n) {
-    __shared__ double red[QP_UW][4][64];
-    const int chain = blockIdx.y;
-    const double* __restrict__ pw = w.pw + (long)chain * w.pw_stride;
-    const double* __restrict__ Vall = pw + (long)QP_SR * n;
-    const double* __restrict__ Tall = Vall + (long)n * n;
-    const double* __restrict__ VTall = Tall + (long)QP_B * n;
-    double* __restrict__ L = Lm.at(chain);
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r16 = lane & 15, kk = lane >> 4;
-    const int cb = blockIdx.x, col = 16 * cb + r16;
-    const int n_tiles = n / 16;
-    d4 Qt[TPW];
-#pragma unroll
-    for (int ti = 0; ti < TPW; ++ti) {
-        const int rt = wave + QP_UW * ti;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Qt[ti][r] = (16 * rt + kk + 4 * r == col) ? 1.0 : 0.0;
-    }
-    double v1[TPW][4], v2[TPW][4], tv[4], n1[TPW][4], n2[TPW][4], nt_[4];
-    auto load = [&](int k, double (&a1)[TPW][4], double (&a2)[TPW][4], double (&at)[4]) {
-        const double* Vp = Vall + (long)n * 16 * k;
-        const double* Tm = Tall + (long)QP_B * 16 * k;
-        const double* VTp = VTall + (long)n * 16 * k;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) at[s] = Tm[r16 + QP_B * (kk + 4 * s)];          // W' = T W: a = T[i' = r16][i = kk + 4 s]
-#pragma unroll
-        for (int ti = 0; ti < TPW; ++ti) {
-            const int rt = wave + QP_UW * ti;
-            const bool in = rt < n_tiles && rt >= k;                                // rows of the factor: 16 k .. n - 1
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                a1[ti][s] = in ? VTp[(long)QP_B * (16 * rt + kk + 4 * s) + r16] : 0.0;
-                a2[ti][s] = in ? Vp[(long)n * (kk + 4 * s) + (16 * rt + r16)] : 0.0;
-            }
-        }
-    };
-    load(cb, v1, v2, tv);
-    for (int k = cb; k >= 0; --k) {
-        if (k > 0) load(k - 1, n1, n2, nt_);
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ti = 0; ti < TPW; ++ti)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v1[ti][s], Qt[ti][s], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[wave][r][lane] = acc[r];
-        __syncthreads();
-        d4 W;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            double v = red[0][r][lane];
-#pragma unroll
-            for (int q = 1; q < QP_UW; ++q) v += red[q][r][lane];
-            W[r] = v;
-        }
-        d4 wp = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) wp = __builtin_amdgcn_mfma_f64_16x16x4f64(tv[s], W[s], wp, 0, 0, 0);
-        wp = -wp;
-#pragma unroll
-        for (int ti = 0; ti < TPW; ++ti)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) Qt[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(v2[ti][s], wp[s], Qt[ti], 0, 0, 0);   // v2 = 0 above the factor's rows
-        __syncthreads();
-#pragma unroll
-        for (int ti = 0; ti < TPW; ++ti)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { v1[ti][s] = n1[ti][s]; v2[ti][s] = n2[ti][s]; }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) tv[s] = nt_[s];
-    }
-#pragma unroll
-    for (int ti = 0; ti < TPW; ++ti) {
-        const int rt = wave + QP_UW * ti;
-        if (rt < n_tiles) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) L[(long)n * col + 16 * rt + kk + 4 * r] = Qt[ti][r];
-        }
-    }
-}
-
-int launch_qr_panel_formq(QrWork w, Mat L, int n, int n_chains, hipStream_t s) {
-    const dim3 grid(n / 16, n_chains);
-    const int tpw = (n / 16 + QP_UW - 1) / QP_UW;
-    if (tpw <= 2) hipLaunchKernelGGL((qp_formq_kernel<2>), grid, dim3(64 * QP_UW), 0, s, w, L, n);
-    else if (tpw <= 5) hipLaunchKernelGGL((qp_formq_kernel<5>), grid, dim3(64 * QP_UW), 0, s, w, L, n);
-    else hipLaunchKernelGGL((qp_formq_kernel<8>), grid, dim3(64 * QP_UW), 0, s, w, L, n);
-    DQ_HIP(hipGetLastError());
-    return 0;
-}
-
 // argument guard of launch_qr_panel: n a multiple of 16 in [16, 1024] and the workspace present
 static bool qr_panel_ok(int n, const QrWork& w) { return n >= 16 && n <= 1024 && n % 16 == 0 && w.pw != nullptr && w.pivpos != nullptr && w.pw_stride >= qr_panel_work_doubles(n); }
-long qr_panel_work_doubles(int n) { return (long)(QP_SR + 2 * n) * n + (long)QP_B * n; }   // Y | V panels | T factors | V panels row-major
+long qr_panel_work_doubles(int n) { return (long)(QP_SR + 3 * n) * n + (long)QP_B * n; }   // Y | V panels | T factors | V panels row-major | Qacc
 
-int launch_qr_panel(Mat A, QrWork w, int n, int n_chains, hipStream_t s) {
+int launch_qr_panel(Mat A, Mat L, QrWork w, int n, int n_chains, hipStream_t s) {
     if (!qr_panel_ok(n, w)) { set_error("panel QR: n must be a multiple of 16 in [16, 1024] and the workspace present"); return -1; }
-    const dim3 ugrid(n / 16, n_chains);
-    const int tpw = (n / 16 + QP_UW - 1) / QP_UW;
-#define QP_UPD(U, K) do { if (tpw <= 2) hipLaunchKernelGGL((qp_update_kernel<U, 2>), ugrid, dim3(64 * QP_UW), 0, s, A, w, n, K); \
-                          else if (tpw <= 5) hipLaunchKernelGGL((qp_update_kernel<U, 5>), ugrid, dim3(64 * QP_UW), 0, s, A, w, n, K); \
-                          else hipLaunchKernelGGL((qp_update_kernel<U, 8>), ugrid, dim3(64 * QP_UW), 0, s, A, w, n, K); } while (0)
-    QP_UPD(false, 0);
+    const int nb = n / 16;
+    const int tpw = (nb + QP_UW - 1) / QP_UW;
+    // GRID column blocks, of which those from QFIRST on have the Q role
+#define QP_UPD(U, K, GRID, QFIRST) do { const dim3 ugrid(GRID, n_chains); \
+                          if (tpw <= 2) hipLaunchKernelGGL((qp_update_kernel<U, 2>), ugrid, dim3(64 * QP_UW), 0, s, A, w, n, K, L, QFIRST); \
+                          else if (tpw <= 5) hipLaunchKernelGGL((qp_update_kernel<U, 5>), ugrid, dim3(64 * QP_UW), 0, s, A, w, n, K, L, QFIRST); \
+                          else hipLaunchKernelGGL((qp_update_kernel<U, 8>), ugrid, dim3(64 * QP_UW), 0, s, A, w, n, K, L, QFIRST); } while (0)
+    QP_UPD(false, 0, nb, nb);
     for (int k = 0; k < n; k += QP_B) {
 #define QP_LAUNCH(NW, CPL) hipLaunchKernelGGL((qp_panel_kernel<NW, CPL>), dim3(1, n_chains), dim3(64 * NW), 0, s, A, w, n, k)
         if (n <= 64) QP_LAUNCH(1, 1); else if (n <= 128) QP_LAUNCH(2, 1); else if (n <= 256) QP_LAUNCH(4, 1); else if (n <= 512) QP_LAUNCH(4, 2);
         else if (n <= 576) QP_LAUNCH(3, 3); else if (n <= 768) QP_LAUNCH(4, 3); else QP_LAUNCH(4, 4);
 #undef QP_LAUNCH
-        if (k + QP_B < n) QP_UPD(true, k);
+        if (k + QP_B < n) QP_UPD(true, k, 2 * nb, nb);             // trailing update | Q accumulation
+        else QP_UPD(true, k, nb, 0);                               // the last panel has no trailing matrix: its factor goes into Q alone
     }
 #undef QP_UPD
     DQ_HIP(hipGetLastError());

@@ -374,6 +374,11 @@ int dqmc_slice_path(dqmc_engine* e);
  * (seq lo, seq hi, error, solo_count, 12 pad, arrive[0..63]); *slice_epoch: launches of that kernel so far.  Any pointer may be
  * NULL.  Synchronises the engine's stream.  No counterpart.                                                              */
 int dqmc_debug_snapshot(dqmc_engine* e, double* wrap_err, int* accepted, unsigned int* sync_words, unsigned int* slice_epoch);
+/* Diagnostic of the transposed copy of G the local-update walk reads.  A stabilisation of the backward sweep writes it from the
+ * product that writes G; while `on` is 1, each of them is followed by a comparison with an explicit transpose of G.  The call
+ * returns, of the checks since the previous call, max_err[n_chains] = max|GT - G^T| (NaN propagates) and *n_checks, clears both,
+ * and sets the switch.  Either pointer may be NULL.  Synchronises the engine's stream.  No counterpart.                    */
+int dqmc_debug_gt_check(dqmc_engine* e, int on, double* max_err, int64_t* n_checks);
 /* enable (1) / disable (0) the per-slice HIP-event timing above (default 0:
  * events serialise nothing but cost a few microseconds per slice).           */
 int dqmc_set_profiling(dqmc_engine* e, int on);
