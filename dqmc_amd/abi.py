@@ -19,6 +19,8 @@ c_double_p = C.POINTER(C.c_double)
 c_int64_p = C.POINTER(C.c_int64)
 c_int32_p = C.POINTER(C.c_int32)
 c_uint8_p = C.POINTER(C.c_uint8)
+c_uint32_p = C.POINTER(C.c_uint32)
+c_uint64_p = C.POINTER(C.c_uint64)
 
 
 class Stats(C.Structure):
@@ -52,6 +54,7 @@ ABI_SYMBOLS = [
     "comm_unique_id", "comm_create_rccl", "comm_create_callbacks", "comm_destroy", "comm_rank", "comm_world_size",
     "comm_transport", "comm_barrier", "comm_allreduce_sum", "comm_selftest", "partner_rank", "replica_exchange_round",
     "replica_exchange_batch",
+    "rng_seed", "rng_state", "rng_draw", "rng_fill_time",
 ]
 
 UNIQUE_ID_BYTES = 128
@@ -142,6 +145,11 @@ class DqmcLib:
             g("replica_exchange_round").argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(ExchangeResult)]
         if self.has_symbol("replica_exchange_batch"):
             g("replica_exchange_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_int, c_double_p, C.POINTER(ExchangeResult)]
+        if self.has_symbol("rng_seed"):
+            g("rng_seed").argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]
+            g("rng_state").argtypes = [C.c_void_p, c_uint64_p, c_uint32_p, c_uint32_p, C.POINTER(C.c_int)]
+            g("rng_draw").argtypes = [C.c_void_p, C.c_uint32, c_int32_p, c_uint8_p, c_double_p]
+            g("rng_fill_time").argtypes = [C.c_void_p, C.c_int, c_double_p]
         g("to_ldr").argtypes = [C.c_int] + [c_double_p] * 4
         g("ldr_mul_mat").argtypes = [C.c_int] + [c_double_p] * 7
         g("mat_mul_ldr").argtypes = [C.c_int] + [c_double_p] * 7
@@ -411,13 +419,43 @@ class Engine:
         u = np.ascontiguousarray(np.asarray(u).reshape(self.C, rows, self.n), dtype=np.float64)
         return perm, kprop, u
 
-    def sweep_0_to_beta(self, perm, kprop, u):
+    def _sweep(self, name, perm, kprop, u):
+        """A half sweep with the given stream; without arguments NULLs are passed: a seeded engine (rng_seed) draws its own."""
+        if perm is None and kprop is None and u is None:
+            self._c(name, None, None, None); return
+        if perm is None or kprop is None or u is None:
+            raise ValueError("pass perm, kprop and u, or none of them")
         perm, kprop, u = self._stream(perm, kprop, u, self.nt)
-        self._c("sweep_0_to_beta", perm.ctypes.data_as(c_int32_p), kprop.ctypes.data_as(c_uint8_p), _p(u))
+        self._c(name, perm.ctypes.data_as(c_int32_p), kprop.ctypes.data_as(c_uint8_p), _p(u))
 
-    def sweep_beta_to_0(self, perm, kprop, u):
-        perm, kprop, u = self._stream(perm, kprop, u, self.nt)
-        self._c("sweep_beta_to_0", perm.ctypes.data_as(c_int32_p), kprop.ctypes.data_as(c_uint8_p), _p(u))
+    def sweep_0_to_beta(self, perm=None, kprop=None, u=None):
+        self._sweep("sweep_0_to_beta", perm, kprop, u)
+
+    def sweep_beta_to_0(self, perm=None, kprop=None, u=None):
+        self._sweep("sweep_beta_to_0", perm, kprop, u)
+
+    # ---- the stream drawn on the device (dqmc_rng_seed; tests/rng_ref.py restates it in numpy) ----
+    def rng_seed(self, seed: int, first_chain: int = 0, counter: int = 0):
+        """Switch to device-drawn streams (or re-position): chain c draws as stream id first_chain + c, the next sweep without
+        arrays is half sweep `counter`."""
+        self._c("rng_seed", C.c_uint64(int(seed)), C.c_uint32(int(first_chain)), C.c_uint32(int(counter)))
+
+    def rng_state(self):
+        """(seed, first_chain, counter, seeded)."""
+        sd = C.c_uint64(0); fc = C.c_uint32(0); ct = C.c_uint32(0); on = C.c_int(0)
+        self._c("rng_state", C.byref(sd), C.byref(fc), C.byref(ct), C.byref(on))
+        return int(sd.value), int(fc.value), int(ct.value), bool(on.value)
+
+    def rng_fill_time(self, launches: int = 20) -> float:
+        """dqmc_rng_fill_time: ms per launch of the kernel that draws one half sweep's stream (HIP events)."""
+        ms = C.c_double(0.0); self._c("rng_fill_time", int(launches), C.byref(ms)); return ms.value
+
+    def rng_draw(self, counter: int):
+        """(perm, kprop, u) the engine uses for half sweep `counter`, shape (nt, n) [(C, nt, n) when batched]; the counter stays."""
+        shape = (self.C, self.nt, self.n)
+        perm = np.empty(shape, np.int32); kprop = np.empty(shape, np.uint8); u = np.empty(shape, np.float64)
+        self._c("rng_draw", C.c_uint32(int(counter)), perm.ctypes.data_as(c_int32_p), kprop.ctypes.data_as(c_uint8_p), _p(u))
+        return (perm, kprop, u) if self.batched else (perm[0], kprop[0], u[0])
 
     def sync(self):
         self._c("sync")

@@ -236,6 +236,12 @@ void slice_release(int device, int n, int n_chains);
 // standalone Sherman-Morrison rank-1 update (source/model.cpp:124-138), whole-chip streaming kernel
 int launch_rank1(Mat G, int i, double delta, double* scratch /*2n+1 doubles per chain*/, long scratch_stride, int n, int n_chains, hipStream_t s);
 
+// ---- rng.hip --------------------------------------------------------------------
+// perm / kprop / u [chains][nt][n] of half-sweep counter h for the chains first_chain .. first_chain + chains - 1 of engine seed `seed`
+// (the stream philox.h states), n <= 1024: one launch, one workgroup per slice and chain
+int launch_rng_fill(int32_t* perm, uint8_t* kprop, double* u, int n, int nt, unsigned long long seed, unsigned first_chain, unsigned h,
+                    int n_chains, hipStream_t s);
+
 // ---- checkerboard.hip -----------------------------------------------------------
 // out = diag(rs_out) * [ E^(+-1) * (diag(rs_in) * in * diag(cs_in)) ] * diag(cs_out), and / or its transpose into outT, where
 // E = f * E_{G-1} ... E_0 is the checkerboard break-up of exp(-dtau K) (README.md:40): E_g mixes the site pairs (r, partner[g][r])

@@ -342,6 +342,9 @@ struct Engine {
     DevPtr<double> logdet;                                       // [C]
     DevPtr<int32_t> rs_perm; DevPtr<uint8_t> rs_k; DevPtr<double> rs_u;   // [C][nt][n]
     PinnedPtr h_stage;                                           // pinned staging for the random stream
+    // dqmc_rng_seed: the stream is drawn on the device (rng.hip) from (rng_seed, rng_first_chain + chain, rng_counter); the counter is the
+    // half sweep the next sweep call without arrays draws
+    bool rng_seeded = false; uint64_t rng_seed = 0; uint32_t rng_first_chain = 0, rng_counter = 0;
     hipEvent_t stage_free = nullptr;
     DevPtr<double> Upanel, Wpanel;                               // [C][KD][n]
     DevPtr<double> Cpanel;                                       // [C][KD][KD]
@@ -658,6 +661,21 @@ struct Engine {
         DQ_HIP(hipMemcpyAsync(rs_perm.get(), hp, cnt * sizeof(int32_t), hipMemcpyHostToDevice, s));
         DQ_HIP(hipMemcpyAsync(rs_k.get(), hk, cnt, hipMemcpyHostToDevice, s));
         DQ_HIP(hipEventRecord(stage_free, s));
+        return 0;
+    }
+    // the stream of half-sweep counter h into rs_*: stream order keeps it behind the readers of the previous half sweep, and nothing
+    // leaves the host, so there is no staging buffer to wait for
+    int fill_stream(uint32_t h) {
+        return launch_rng_fill(rs_perm.get(), rs_k.get(), rs_u.get(), n, nt, rng_seed, rng_first_chain, h, C, s);
+    }
+    // the random stream of a sweep call: explicit arrays are uploaded; all three NULL draws the next half sweep of a seeded engine
+    int stage_stream(const char* who, const int32_t* perm, const uint8_t* kprop, const double* u) {
+        if (perm && kprop && u) return upload_stream(perm, kprop, u);
+        if (perm || kprop || u) { set_error(std::string(who) + ": pass all three random-stream arrays or none"); return DQMC_EINVAL; }
+        if (!rng_seeded) { set_error(std::string(who) + ": null random-stream pointer (the engine draws its own stream only after dqmc_rng_seed)"); return DQMC_EINVAL; }
+        if (rng_counter == UINT32_MAX) { set_error(std::string(who) + ": the half-sweep counter of this seed is used up (2^32 - 1)"); return DQMC_ERANGE; }
+        DQ_TRY(fill_stream(rng_counter));
+        ++rng_counter;
         return 0;
     }
     // DQMC::sweep_0_to_beta (source/dqmc.cpp:337-396)
@@ -1038,14 +1056,42 @@ int dqmc_get_stack(dqmc_engine* h, int i, double* L, double* d, double* R) {
 int dqmc_sweep_0_to_beta(dqmc_engine* h, const int32_t* perm, const uint8_t* kprop, const double* u) {
     ENGINE_CALL(h);
     if (!e.stack_valid) { set_error("dqmc_init must be called before sweeping"); return DQMC_EINVAL; }
-    DQ_TRY(e.upload_stream(perm, kprop, u)); return e.sweep_fwd();
+    DQ_TRY(e.stage_stream("sweep_0_to_beta", perm, kprop, u)); return e.sweep_fwd();
 }
 int dqmc_sweep_beta_to_0(dqmc_engine* h, const int32_t* perm, const uint8_t* kprop, const double* u) {
     ENGINE_CALL(h);
     if (!e.stack_valid) { set_error("dqmc_init must be called before sweeping"); return DQMC_EINVAL; }
-    DQ_TRY(e.upload_stream(perm, kprop, u)); return e.sweep_bwd();
+    DQ_TRY(e.stage_stream("sweep_beta_to_0", perm, kprop, u)); return e.sweep_bwd();
 }
 int dqmc_sync(dqmc_engine* h) { ENGINE_CALL(h); return e.sync_and_check(); }
+int dqmc_rng_seed(dqmc_engine* h, uint64_t seed, uint32_t first_chain, uint32_t counter) {
+    ENGINE_CALL(h);
+    if ((uint64_t)first_chain + (uint64_t)e.C - 1 > UINT32_MAX) { set_error("rng_seed: first_chain + n_chains - 1 exceeds 32 bits"); return DQMC_EINVAL; }
+    e.rng_seeded = true; e.rng_seed = seed; e.rng_first_chain = first_chain; e.rng_counter = counter;
+    return 0;
+}
+int dqmc_rng_state(dqmc_engine* h, uint64_t* seed, uint32_t* first_chain, uint32_t* counter, int* seeded) {
+    if (!h) { set_error("null engine"); return DQMC_EINVAL; }
+    const Engine& e = h->e;
+    if (seed) *seed = e.rng_seed;
+    if (first_chain) *first_chain = e.rng_first_chain;
+    if (counter) *counter = e.rng_counter;
+    if (seeded) *seeded = e.rng_seeded ? 1 : 0;
+    return 0;
+}
+int dqmc_rng_draw(dqmc_engine* h, uint32_t counter, int32_t* perm, uint8_t* kprop, double* u) {
+    ENGINE_CALL(h);
+    if (!perm || !kprop || !u) { set_error("rng_draw: null pointer"); return DQMC_EINVAL; }
+    if (!e.rng_seeded) { set_error("rng_draw: the engine has no seed (dqmc_rng_seed)"); return DQMC_EINVAL; }
+    // rs_* are scratch between sweep calls: every sweep fills or uploads them before it reads them
+    DQ_TRY(e.fill_stream(counter));
+    DQ_TRY(e.sync_and_check());
+    const size_t cnt = (size_t)e.C * e.nt * e.n;
+    DQ_HIP(hipMemcpy(perm, e.rs_perm.get(), cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    DQ_HIP(hipMemcpy(kprop, e.rs_k.get(), cnt, hipMemcpyDeviceToHost));
+    DQ_HIP(hipMemcpy(u, e.rs_u.get(), cnt * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
 int dqmc_get_stats(dqmc_engine* h, dqmc_stats* out) {
     ENGINE_CALL(h); DQ_TRY(e.sync_and_check());
     static_assert(sizeof(DevStats) == sizeof(dqmc_stats), "stats layout");
@@ -1077,6 +1123,24 @@ int dqmc_local_update_slice(dqmc_engine* h, int l, const int32_t* perm, const ui
     DQ_TRY(e.sync_and_check());
     if (accepted) for (int c = 0; c < e.C; ++c) DQ_HIP(hipMemcpy(accepted + c, e.acc.get() + (size_t)c * e.nt + l, sizeof(int), hipMemcpyDeviceToHost));
     return 0;
+}
+int dqmc_rng_fill_time(dqmc_engine* h, int launches, double* ms_per_launch) {
+    ENGINE_CALL(h);
+    if (launches < 1 || !ms_per_launch) { set_error("rng_fill_time: launches >= 1 and a result pointer"); return DQMC_EINVAL; }
+    if (!e.rng_seeded) { set_error("rng_fill_time: the engine has no seed (dqmc_rng_seed)"); return DQMC_EINVAL; }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DQ_HIP(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("rng_fill_time: hipEventCreate failed"); return DQMC_ENODEVICE; }
+    int rc = e.fill_stream(e.rng_counter);                          // first launch of the kernel outside the timed window
+    if (rc == 0 && hipEventRecord(e0, e.s) != hipSuccess) rc = DQMC_ENODEVICE;
+    for (int k = 0; k < launches && rc == 0; ++k) rc = e.fill_stream(e.rng_counter);
+    if (rc == 0 && hipEventRecord(e1, e.s) != hipSuccess) rc = DQMC_ENODEVICE;
+    if (rc == 0) rc = e.sync_and_check();
+    float ms = 0.f;
+    if (rc == 0 && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = DQMC_ENODEVICE;
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (rc == 0) *ms_per_launch = (double)ms / launches;
+    return rc;
 }
 int dqmc_calculate_Bbar(dqmc_engine* h, int is, double* out) {
     ENGINE_CALL(h);

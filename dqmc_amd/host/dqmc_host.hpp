@@ -400,6 +400,7 @@ class DQMC {
     int nt_, n_stab_, n_stack_;
     bool isUnequalTime_ = false;
     std::vector<int32_t> perm_; std::vector<uint8_t> kprop_; std::vector<double> u_;
+    bool device_rng_ = false;
     void draw_half_sweep(bool forward) {
         const int ns = model_.ns();
         for (int step = 0; step < nt_; ++step) {
@@ -449,8 +450,19 @@ public:
     // pulls the device's HS fields back into model.fields() (they change on device during sweeps)
     void download_fields() { dqmc_detail::check(dqmc_get_fields(e_, model_.fields().fields_mut().data())); }
     // source/dqmc.cpp:337-396 / :398-456; asynchronous, greens are refreshed by download()
-    void sweep_0_to_beta(std::vector<GF>&, std::vector<LDRStack>&) { draw_half_sweep(true); dqmc_detail::check(dqmc_sweep_0_to_beta(e_, perm_.data(), kprop_.data(), u_.data())); }
-    void sweep_beta_to_0(std::vector<GF>&, std::vector<LDRStack>&) { draw_half_sweep(false); dqmc_detail::check(dqmc_sweep_beta_to_0(e_, perm_.data(), kprop_.data(), u_.data())); }
+    void sweep_0_to_beta(std::vector<GF>&, std::vector<LDRStack>&) {
+        if (device_rng_) { dqmc_detail::check(dqmc_sweep_0_to_beta(e_, nullptr, nullptr, nullptr)); return; }
+        draw_half_sweep(true); dqmc_detail::check(dqmc_sweep_0_to_beta(e_, perm_.data(), kprop_.data(), u_.data()));
+    }
+    void sweep_beta_to_0(std::vector<GF>&, std::vector<LDRStack>&) {
+        if (device_rng_) { dqmc_detail::check(dqmc_sweep_beta_to_0(e_, nullptr, nullptr, nullptr)); return; }
+        draw_half_sweep(false); dqmc_detail::check(dqmc_sweep_beta_to_0(e_, perm_.data(), kprop_.data(), u_.data()));
+    }
+    // No counterpart in the reference: from now on the engine draws the stream of every half sweep itself (dqmc_rng_seed, stream id
+    // `chain`), sweep_* no longer touch model.rng() and upload nothing.  The host generator keeps drawing the initial fields and the
+    // exchange decisions.  rng_counter(): half sweeps drawn so far -- with (seed, chain) the generator's whole state.
+    void use_device_rng(uint64_t seed, uint32_t chain) { dqmc_detail::check(dqmc_rng_seed(e_, seed, chain, 0)); device_rng_ = true; }
+    uint32_t rng_counter() { uint32_t h = 0; dqmc_detail::check(dqmc_rng_state(e_, nullptr, nullptr, &h, nullptr)); return h; }
     // source/dqmc.cpp:458-515: a no-op unless [simulation] isMeasureUnequalTime = true (:461-463); the Gtt / Gt0 / G0t series stay in HBM,
     // download_tau() fetches one slice (GF::Gtt[l], Gt0[l], G0t[l] of include/stackngf.h:15-29)
     void sweep_unequalTime(std::vector<GF>&, std::vector<LDRStack>&) { if (isUnequalTime_) dqmc_detail::check(dqmc_sweep_unequal_time(e_)); }

@@ -3,6 +3,7 @@
 // model constants, replica pairing) without a GPU.  No HIP, no oracle.
 #include "dqmc_host.hpp"
 #include "results_h5.hpp"
+#include "../csrc/philox.h"
 
 #include <cstdio>
 #include <memory>
@@ -48,6 +49,24 @@ int dqmc_host_bernoulli_check(unsigned int seed, int n, const double* p) {
     }
     if (a.get_generator()() != b.get_generator()()) ++diff;
     return diff;
+}
+
+// the device-drawn stream (dqmc_rng_seed) on the host, from the text the fill kernel compiles (csrc/philox.h): one Philox4x32-10
+// block, and perm / kprop / u [nt][n] of (seed, chain id g, half-sweep counter h) with the permutation by std::sort on (key64, site)
+void dqmc_host_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
+    const dq::Philox4 r = dq::philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1]);
+    for (int k = 0; k < 4; ++k) out[k] = r.x[k];
+}
+void dqmc_host_rng_stream(uint64_t seed, uint32_t g, uint32_t h, int nt, int n, int32_t* perm, uint8_t* kprop, double* u) {
+    std::vector<std::pair<uint64_t, int32_t>> rec((size_t)n);
+    for (int l = 0; l < nt; ++l) {
+        for (int i = 0; i < n; ++i) {
+            dq::rng_proposal(seed, g, h, (uint32_t)l, (uint32_t)i, u + (size_t)l * n + i, kprop + (size_t)l * n + i);
+            rec[i] = {dq::rng_perm_key(seed, g, h, (uint32_t)l, (uint32_t)i), (int32_t)i};
+        }
+        std::sort(rec.begin(), rec.end());
+        for (int i = 0; i < n; ++i) perm[(size_t)l * n + i] = rec[i].second;
+    }
 }
 
 int dqmc_host_partner_rank(int rank, int world, int attempt) { return update::partner_rank(rank, world, attempt); }

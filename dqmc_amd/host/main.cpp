@@ -111,6 +111,10 @@ int run_rank(const RunConfig& rc, int rank, int world_size, int device, dqmc_com
     AttractiveHubbard model(params, lat, rng, my_beta);
     const int n_flavor = model.n_flavor();
     DQMC sim(params, model, device);
+    // extension key, like checkerboard: the per-slice stream is drawn on the device (stream id = rank); `rng` still draws the initial
+    // fields (above) and the exchange decisions
+    const bool device_rng = params.getBool("simulation", "device_rng", false);
+    if (device_rng) sim.use_device_rng(rc.seed, (uint32_t)rank);
 
     std::vector<LDRStack> propagation_stacks(n_flavor);
     std::vector<GF> greens(n_flavor);
@@ -185,6 +189,7 @@ int run_rank(const RunConfig& rc, int rank, int world_size, int device, dqmc_com
         std::lock_guard<std::mutex> lk(g_print_mu);
         std::cout << "rank " << rank << ": Max, Mean Precision Error = " << std::scientific << std::setprecision(4) << sim.max_err() << ", " << sim.mean_err()
                   << std::fixed << ", acceptance " << local_acc_rate << '\n';
+        if (device_rng) std::cout << "rank " << rank << ": rng seed " << rc.seed << " chain " << rank << " counter " << sim.rng_counter() << '\n';   // the run's position in its stream
     }
     if (rank == master) {
         std::lock_guard<std::mutex> lk(g_print_mu);

@@ -14,7 +14,11 @@ driver (dqmc_amd/host/main.cpp) is the same loop without Python.
 world has world_size * K replicas and dqmc_replica_exchange_batch runs the rounds -- pairs inside an engine swap on the
 device, chain 0 / chain K-1 pair with the neighbour ranks over the communicator.  On one process no communicator is needed:
 
-    python dqmc_amd/pt_run.py --replicas-per-gpu 8 --sweeps 40 --sweep-steps 5"""
+    python dqmc_amd/pt_run.py --replicas-per-gpu 8 --sweeps 40 --sweep-steps 5
+
+--device-rng: the engines draw the per-slice random stream themselves (dqmc_rng_seed: seed as given, stream id = the replica
+index, i.e. first_chain = rank * K), so no stream is drawn in Python or uploaded; the numpy generators keep drawing the initial
+fields and the exchange uniforms."""
 from __future__ import annotations
 
 import argparse
@@ -41,7 +45,8 @@ def gloo_sendrecv(dist):
     return sendrecv
 
 
-def run_pt(d, lib, betas, L, U, nt, n_stab, therm, sweeps, sweep_steps, seed=1234, log=print, transport="rccl", device=None):
+def run_pt(d, lib, betas, L, U, nt, n_stab, therm, sweeps, sweep_steps, seed=1234, log=print, transport="rccl", device=None,
+           device_rng=False):
     """Returns (sweeps/s of the slowest rank, exchange_attempt, exchange_accepted of rank 0's pairs).  transport: "rccl" (one GPU per
     rank, fields HBM to HBM) or "callbacks" (dqmc_comm_create_callbacks over torch.distributed point-to-point)."""
     import torch.distributed as dist
@@ -61,9 +66,14 @@ def run_pt(d, lib, betas, L, U, nt, n_stab, therm, sweeps, sweep_steps, seed=123
     eng = model.engine(lib, device=dev)
     eng.set_fields(model.random_fields(seed + d.rank)); eng.init()
     rng = np.random.default_rng(seed + 1000 + d.rank)
+    if device_rng:
+        eng.rng_seed(seed, first_chain=d.rank)
 
     def sweep():
-        eng.sweep_0_to_beta(*model.random_stream(rng)); eng.sweep_beta_to_0(*model.random_stream(rng))
+        if device_rng:
+            eng.sweep_0_to_beta(); eng.sweep_beta_to_0()
+        else:
+            eng.sweep_0_to_beta(*model.random_stream(rng)); eng.sweep_beta_to_0(*model.random_stream(rng))
 
     for _ in range(therm):
         sweep()
@@ -96,7 +106,8 @@ def run_pt(d, lib, betas, L, U, nt, n_stab, therm, sweeps, sweep_steps, seed=123
     return sweeps / dt, attempt, accepted
 
 
-def run_pt_batched(d, lib, betas, K, L, U, nt, n_stab, therm, sweeps, sweep_steps, seed=1234, log=print, transport="rccl", device=None):
+def run_pt_batched(d, lib, betas, K, L, U, nt, n_stab, therm, sweeps, sweep_steps, seed=1234, log=print, transport="rccl", device=None,
+                   device_rng=False):
     """run_pt with K replicas per rank in one batched engine: replica g = rank*K + c has betas[g], its own fields and generator
     (seeded as run_pt seeds rank g).  Returns (replica sweeps/s of this rank's engine over the slowest rank's time, exchange_attempt,
     accepted swaps of replica 0)."""
@@ -122,8 +133,13 @@ def run_pt_batched(d, lib, betas, K, L, U, nt, n_stab, therm, sweeps, sweep_step
                      np.stack([m.invexpK for m in ms]), device=dev, n_chains=K)
     eng.set_fields(np.stack([m.random_fields(seed + g) for m, g in zip(ms, gs)])); eng.init()
     rngs = [np.random.default_rng(seed + 1000 + g) for g in gs]
+    if device_rng:
+        eng.rng_seed(seed, first_chain=d.rank * K)
 
     def sweep():
+        if device_rng:
+            eng.sweep_0_to_beta(); eng.sweep_beta_to_0()
+            return
         for fn in (eng.sweep_0_to_beta, eng.sweep_beta_to_0):
             st = [ms[c].random_stream(rngs[c]) for c in range(K)]
             fn(*(np.stack([x[k] for x in st]) for k in range(3)))
@@ -187,6 +203,9 @@ def main():
     ap.add_argument("--sweep-steps", type=int, default=5)
     ap.add_argument("--replicas-per-gpu", type=int, default=1,
                     help="betas per rank, held as the chains of one batched engine (1: one single-chain engine per rank)")
+    ap.add_argument("--device-rng", action="store_true",
+                    help="draw the per-slice random stream on the device (dqmc_rng_seed) instead of in Python")
+    ap.add_argument("--seed", type=int, default=1234)
     args = ap.parse_args()
     import dqmc_amd
     from dqmc_amd.launch import dist_init, finalize
@@ -194,9 +213,10 @@ def main():
     betas = [float(b) for b in args.betas.split(",") if b.strip()]
     if args.replicas_per_gpu > 1:
         run_pt_batched(d, dqmc_amd.lib(), betas, args.replicas_per_gpu, args.L, args.U, args.nt, args.n_stab, args.therm, args.sweeps,
-                       args.sweep_steps)
+                       args.sweep_steps, seed=args.seed, device_rng=args.device_rng)
     else:
-        run_pt(d, dqmc_amd.lib(), betas, args.L, args.U, args.nt, args.n_stab, args.therm, args.sweeps, args.sweep_steps)
+        run_pt(d, dqmc_amd.lib(), betas, args.L, args.U, args.nt, args.n_stab, args.therm, args.sweeps, args.sweep_steps, seed=args.seed,
+               device_rng=args.device_rng)
     finalize(d)
 
 

@@ -188,6 +188,39 @@ int dqmc_sweep_beta_to_0(dqmc_engine* e, const int32_t* perm, const uint8_t* kpr
 int dqmc_sync(dqmc_engine* e);
 int dqmc_get_stats(dqmc_engine* e, dqmc_stats* out);
 
+/* ---- the random stream drawn on the device (opt-in; no counterpart in the reference) ----
+ * An engine that has been given a seed draws perm / kprop / u itself, one kernel launch per half sweep, and nothing is
+ * uploaded: call dqmc_sweep_0_to_beta / dqmc_sweep_beta_to_0 with all three arrays NULL.  An engine that was never seeded
+ * refuses NULL arrays with DQMC_EINVAL as before, some NULL and some not is DQMC_EINVAL on every engine, and explicit
+ * arrays keep working on a seeded engine without advancing its counter.  dqmc_local_update_slice always takes arrays.
+ * The generator is Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl increments 0x9E3779B9, 0xBB67AE85; 10 rounds)
+ * with key (seed & 0xffffffff, seed >> 32).  For chain c of the engine, g = first_chain + c, half-sweep counter h, slice l:
+ *   position idx of the visiting order: counter (idx, l, h, g) -> x0 .. x3;
+ *       u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53, in [0, 1) on a 2^-53 grid;
+ *       kprop = (x2 * 3) >> 32 as a 64-bit product (the three values differ in probability by at most 2^-32); x3 unused
+ *   site i: counter (i, l | 0x80000000, h, g) -> key64 = x0 << 32 | x1;
+ *       perm[l][.] = the sites sorted ascending by (key64, i): a uniform permutation, the site index breaks ties
+ *       (probability about n^2 2^-65), and that rule is part of the stream
+ * indexed [c][l][idx] like the host stream above, in the backward sweep too.  One device-drawn half sweep uses exactly one
+ * value of h, so (seed, g, h) is the whole state of a chain's generator: a run resumes from its fields and these integers.
+ * A replica exchange moves the fields; the chain keeps its stream id g and its counter, as it keeps its beta and its stats. */
+
+/* Switches the engine to device-drawn streams, or re-positions it: the next sweep without arrays draws half sweep
+ * `counter`.  first_chain + n_chains - 1 must fit 32 bits.  No counterpart in the reference.                             */
+int dqmc_rng_seed(dqmc_engine* e, uint64_t seed, uint32_t first_chain, uint32_t counter);
+/* The generator's position: *seeded = 0 for an engine dqmc_rng_seed was never called on (the other values are 0 then).
+ * Any pointer may be NULL.  The last value of the counter, 2^32 - 1, means "used up": a sweep without arrays then returns
+ * DQMC_ERANGE and leaves the chain untouched.  No counterpart in the reference.                                          */
+int dqmc_rng_state(dqmc_engine* e, uint64_t* seed, uint32_t* first_chain, uint32_t* counter, int* seeded);
+/* The stream the engine uses for half sweep `counter`, as host arrays [n_chains][nt][n_sites] (the kernel of the sweeps
+ * plus a download): for tests, replays on other engines and post-mortems.  Synchronous; does not advance the counter.
+ * DQMC_EINVAL when the engine has no seed.  No counterpart in the reference.                                             */
+int dqmc_rng_draw(dqmc_engine* e, uint32_t counter, int32_t* perm, uint8_t* kprop, double* u);
+/* Diagnostic: the time of one launch of the kernel that draws a half sweep's stream, in ms, as the mean over `launches`
+ * back-to-back launches between two HIP events on the engine's stream (scripts/rng_time.py).  Draws the current counter's
+ * stream into the engine's buffers and leaves the counter alone.  Synchronous.  No counterpart in the reference.         */
+int dqmc_rng_fill_time(dqmc_engine* e, int launches, double* ms_per_launch);
+
 /* Fine-grained steps of the sweep, for parity tests and custom drivers.      */
 /* DQMC::propagate_GF_forward / _backward (source/dqmc.cpp:113-132,169-187).  */
 int dqmc_wrap_forward(dqmc_engine* e, int l);
