@@ -133,10 +133,13 @@ struct QrWork {
     unsigned long long* sync = nullptr; long sync_stride = 0;   // cooperative QRCP: granule records, >= qrcp_coop_sync_granules(n) per chain
     int* abort_words = nullptr;                                 // cooperative QRCP: one word per chain
     int* info = nullptr;                                        // status block: |= DQ_STATUS_COOP_QR when a cooperative factorisation gave up waiting
-    double* pw = nullptr; long pw_stride = 0;                   // panel-pivoted QR (qr_panel.hip): sketch, clean reflector panels, T, Q accumulator; >= qr_panel_work_doubles(n) per chain
+    double* pw = nullptr; long pw_stride = 0;                   // panel-pivoted QR (qr_panel.hip): sketches, Q accumulator, ticket counter (zero between calls); >= qr_panel_work_doubles(n, pw_two_launch) per chain
+    bool pw_two_launch = false;                                 // ... with room for the reflector panels and T factors: the two-launch form (panel kernel + update kernel) is used at every n
     int* pivpos = nullptr; long pivpos_stride = 0;              // panel-pivoted QR: pivot position of every column (-1 = live), n per chain
 };
-long qr_panel_work_doubles(int n);
+bool qr_panel_fused_fits(int n);             // the one-launch-per-panel form has an instance for this n
+bool qr_panel_fused_default(int n);          // ... and is what to_LDR uses at this n unless DQMC_QR_PANEL_FUSED says otherwise
+long qr_panel_work_doubles(int n, bool two_launch);
 int launch_qr_panel(Mat A, Mat L, QrWork w, int n, int n_chains, hipStream_t s);   // qr_panel.hip: A -> reflectors / R0 in place, tau, jpvt (same format as the QRCP kernels); L = the explicit Q
 long qrcp_coop_sync_granules(int n);        // granules of cooperative-QRCP workspace per chain
 int qrcp_coop_workgroups(int n, int n_chains);

@@ -40,11 +40,12 @@ int init_device_kernels(int device) {
 // Kernel families of to_LDR, the solves and the local update, decided here and nowhere else (the per-size instance inside a family
 // is chosen next to its kernel) from n, the chain count, the CU reservation and the switches (README.md, "Environment switches").
 // ---------------------------------------------------------------------------
-struct Switches { bool qr_panel, qr_streaming, walk_submatrix, lu_classic, slice_multikernel; };
+struct Switches { bool qr_panel; int qr_panel_fused; bool qr_streaming, walk_submatrix, lu_classic, slice_multikernel; };
 static const Switches& switches() {           // read once per process
     static const Switches sw = [] {
         const char* panel = getenv("DQMC_QR_PANEL");
-        return Switches{!(panel && atoi(panel) == 0), getenv("DQMC_QR_STREAMING") != nullptr, getenv("DQMC_WALK_SUBMATRIX") != nullptr,
+        const char* fused = getenv("DQMC_QR_PANEL_FUSED");          // unset (-1): where it measured faster; 0: nowhere; 1: wherever an instance exists
+        return Switches{!(panel && atoi(panel) == 0), fused ? (atoi(fused) != 0 ? 1 : 0) : -1, getenv("DQMC_QR_STREAMING") != nullptr, getenv("DQMC_WALK_SUBMATRIX") != nullptr,
                         getenv("DQMC_LU_CLASSIC") != nullptr, getenv("DQMC_SLICE_MULTIKERNEL") != nullptr};
     }();
     return sw;
@@ -144,7 +145,8 @@ struct Ctx {
     DevPtr<unsigned long long> qsync;          // cooperative QRCP records
     DevPtr<int> qabort;                        // cooperative QRCP abort words: C
     DevPtr<double> tinv;                       // Gauss-Jordan panel inverses: 2048 * C
-    DevPtr<double> qpw;                        // panel-pivoted QR (qr_panel.hip): qr_panel_work_doubles(n) * C
+    DevPtr<double> qpw;                        // panel-pivoted QR (qr_panel.hip): qr_panel_work_doubles(n, qpw_two_launch) * C, zeroed (the ticket counters)
+    bool qpw_two_launch = false;               // ... in the two-launch form (panel kernel + update kernel): sizes the fused step is not used at, or DQMC_QR_PANEL_FUSED=0
     DevPtr<int> qpivpos;                       // ... and its pivot positions: n * C
     DevPtr<double> trinv;                      // blocked triangular solve: inverses of the 16 x 16 diagonal blocks, 16 * (n + 16) * C
     KernelPlan plan{};                         // the kernel families of this (n, C); each family's workspace above exists only when chosen
@@ -166,7 +168,13 @@ struct Ctx {
         DQ_TRY(dev_alloc(ipool, 3L * C * n + 4));
         plan = KernelPlan::pick(n, C);
         if (plan.qr == QrFamily::Cooperative) { DQ_TRY(dev_alloc(qsync, (size_t)qrcp_coop_sync_granules(n) * C)); DQ_TRY(dev_alloc(qabort, C)); }
-        if (plan.qr == QrFamily::Panel) { DQ_TRY(dev_alloc(qpw, (size_t)qr_panel_work_doubles(n) * C)); DQ_TRY(dev_alloc(qpivpos, (size_t)n * C)); }
+        if (plan.qr == QrFamily::Panel) {
+            const int fused = switches().qr_panel_fused;
+            qpw_two_launch = !(fused < 0 ? qr_panel_fused_default(n) : fused == 1 && qr_panel_fused_fits(n));
+            const size_t qpw_count = (size_t)qr_panel_work_doubles(n, qpw_two_launch) * C;
+            DQ_TRY(dev_alloc(qpw, qpw_count)); DQ_TRY(dev_alloc(qpivpos, (size_t)n * C));
+            DQ_HIP(hipMemsetAsync(qpw.get(), 0, sizeof(double) * qpw_count, stream));
+        }
         if (plan.solve == KernelPlan::Solve::GaussJordan) DQ_TRY(dev_alloc(tinv, (size_t)2048 * C));
         if (plan.rinv == KernelPlan::Rinv::Blocked) DQ_TRY(dev_alloc(trinv, (size_t)16 * (n + 16) * C));
         DQ_HIP(hipMemsetAsync(ipool.get(), 0, sizeof(int) * (3L * C * n + 4), stream));
@@ -185,7 +193,7 @@ struct Ctx {
         const bool keep = direct && out.jpvt != nullptr;
         QrWork w{V(4).p, (long)n, keep ? out.jpvt : jpvt(), (long)n};
         w.sync = qsync.get(); w.sync_stride = qrcp_coop_sync_granules(n); w.abort_words = qabort.get(); w.info = info();
-        w.pw = qpw.get(); w.pw_stride = qr_panel_work_doubles(n); w.pivpos = qpivpos.get(); w.pivpos_stride = n;
+        w.pw = qpw.get(); w.pw_stride = qr_panel_work_doubles(n, qpw_two_launch); w.pw_two_launch = qpw_two_launch; w.pivpos = qpivpos.get(); w.pivpos_stride = n;
         if (out.tri) *out.tri = keep;
         out.touch();
         return launch_to_ldr(plan.qr, A, out.L, out.d, out.R, w, n, C, stream);

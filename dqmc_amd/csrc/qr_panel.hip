@@ -24,6 +24,10 @@
 // 892), 2.0 ms at n = 576 (qr_coop: 4.26).  Where the time goes, and the forms that were measured and dropped (one persistent launch, a lane pair per
 // sketch column, 24 sketch rows, look-ahead selection): DESIGN.md section 5.
 //
+// One launch per panel up to n = 512 (qp_step_kernel: the update launch, every workgroup of which factors the panel itself -- no hand-over,
+// no reflector panels in global memory; 29.6 against 25.2 + 6.5 us per panel at n = 256); the pair of launches above that and under
+// DQMC_QR_PANEL_FUSED=0.  Both forms give the same bits.
+//
 // Randomised panel pivoting (Duersch & Gu 2017; Martinsson, Quintana-Orti, Heavner, van de Geijn 2017).  The numpy statement
 // of exactly this algorithm is oracle/panel_qr.py::qr_sketch(b = 16, p = 16, sign = True, local_pivot = False); its effect on
 // G (cfg 3 thermalised sweep 3e-11 absolute, cfg 3 / cfg 5 i.i.d. <= 3e-11 relative; tournament pivoting and Gaussian sketches
@@ -281,26 +285,35 @@ __device__ __forceinline__ void panel_step(double (&a)[CPL][16], double (&trow)[
 
 }  // namespace
 
-// One workgroup of NW waves per chain (64 NW CPL >= n: a lane owns CPL columns in the selection and CPL 16-row blocks of one column in
-// the panel): selects the 16 columns of the panel that starts at step k and factors them.
-template <int NW, int CPL>
-__global__ __launch_bounds__(64 * NW) void qp_panel_kernel(Mat Am, QrWork w, int n, int k) {
-    __shared__ PanelShared<NW> sh;
-    const int chain = blockIdx.y;
-    double* __restrict__ A = Am.at(chain);
-    double* __restrict__ pw = w.pw + (long)chain * w.pw_stride;
-    const double* __restrict__ Y = pw;                         // [QP_SR][n]
-    double* __restrict__ Vp = pw + (long)QP_SR * n + (long)n * k;                 // [n][QP_B] column-major clean copy of THIS panel's reflectors
-    double* __restrict__ Tm = pw + (long)QP_SR * n + (long)n * n + (long)QP_B * k;   // [QP_B][QP_B] column-major, one per panel
-    double* __restrict__ VTp = pw + (long)QP_SR * n + (long)n * n + (long)QP_B * n + (long)n * k;   // the same panel row-major ([n][QP_B]): the operand of V^T A is read along its rows
-    int* __restrict__ pivpos = w.pivpos + (long)chain * w.pivpos_stride;
-    double* tau = w.tau + (long)chain * w.tau_stride;
-    int* jpvt = w.jpvt + (long)chain * w.jpvt_stride;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+// per-chain workspace (doubles): the sketch Y [QP_SR][n], twice (the fused step reads the buffer of the panel's parity and writes the other
+// one) | Qacc [n][n] | the ticket counter of the fused step (one word, 16-byte slot) | two-launch form only: the clean reflector panels
+// column-major [n][n] | the T factors [QP_B][n] | the panels row-major [n][n]
+__host__ __device__ __forceinline__ long qp_off_qacc(int n) { return 2L * QP_SR * n; }
+__host__ __device__ __forceinline__ long qp_off_ticket(int n) { return qp_off_qacc(n) + (long)n * n; }
+__host__ __device__ __forceinline__ long qp_off_vp(int n) { return qp_off_ticket(n) + 2; }
+__host__ __device__ __forceinline__ long qp_off_tm(int n) { return qp_off_vp(n) + (long)n * n; }
+__host__ __device__ __forceinline__ long qp_off_vtp(int n) { return qp_off_tm(n) + (long)QP_B * n; }
 
 #ifdef DQ_QP_STAMPS
-    __shared__ unsigned long long qst[40];
+#define QP_QST_PARAM , unsigned long long* qst
+#define QP_QST_ARG , qst
+#else
+#define QP_QST_PARAM
+#define QP_QST_ARG
 #endif
+
+// The selection and the factorisation of the panel that starts at step k, by one workgroup of NW waves (64 NW CPL >= n: a lane owns CPL
+// columns in the selection and CPL 16-row blocks of one column in the panel).  Reads Y, pivpos and rows >= k of the selected columns of A;
+// writes nothing but tau_out[0..15] and leaves the factored panel in registers: lane (c, g) of every wave holds a[b][i] = rows
+// 64 NW b + 64 wave + 16 g + i of column mycol = sel[c] (R0 / beta on and above the column's diagonal, the UNSCALED reflector tail below:
+// times myscale), wave 0 holds row c of T in trow.  Every global load has landed when step 0 of the panel passes its barrier;
+// pre() runs once the first round of loads (sketch, pivpos) is issued and before anything is waited for -- true: the workgroup leaves, the
+// function returns false --, mid() right after step 0 of the panel.  qp_panel_kernel and qp_step_kernel both call this body, so they factor bit for bit alike.
+template <int NW, int CPL, class Pre, class Mid>
+__device__ __forceinline__ bool qp_factor_panel(const double* A, const double* __restrict__ Y, const int* pivpos, int n, int k, PanelShared<NW>& sh,
+                                                double* tau_out, double (&a)[CPL][16], double (&trow)[QP_B], double& myscale, unsigned& diag, int& mycol,
+                                                Pre&& pre, Mid&& mid QP_QST_PARAM) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     QST(0)
     // ---- selection ----
     {
@@ -313,6 +326,7 @@ __global__ __launch_bounds__(64 * NW) void qp_panel_kernel(Mat Am, QrWork w, int
             for (int i = 0; i < QP_SEL; ++i) y[q][i] = Y[(long)i * n + cc];
             pp[q] = pivpos[cc];
         }
+        if (pre()) return false;                                     // (workgroup-uniform)
 #pragma unroll
         for (int q = 0; q < CPL; ++q) {
             const int col = t + 64 * NW * q;
@@ -332,9 +346,9 @@ __global__ __launch_bounds__(64 * NW) void qp_panel_kernel(Mat Am, QrWork w, int
     lds_barrier();
     // ---- panel ----
     const int c = lane & 15, g = lane >> 4;
-    const int mycol = sh.sel[c];
-    double a[CPL][16], trow[QP_B], myscale = 0.0;
-    unsigned diag = 0u, blk_live = 0u;
+    mycol = sh.sel[c];
+    myscale = 0.0; diag = 0u;
+    unsigned blk_live = 0u;
 #pragma unroll
     for (int b = 0; b < CPL; ++b) {
         const int r0 = 64 * NW * b + 64 * wave + 16 * g;
@@ -346,17 +360,45 @@ __global__ __launch_bounds__(64 * NW) void qp_panel_kernel(Mat Am, QrWork w, int
         for (int i = 0; i < 16; i += 2) { const double2 v = rows_live ? src[i >> 1] : double2{0.0, 0.0}; a[b][i] = v.x; a[b][i + 1] = v.y; }
         dpp_fence(a[b]);
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // every wave, also one whose blocks all lie above the panel: nothing of this workgroup's is in flight past step 0
 #pragma unroll
     for (int i = 0; i < QP_B; ++i) trow[i] = 0.0;
-    double* tau_out = tau + k;
 #ifdef DQ_QP_STAMPS
     if (a[0][0] == 1.2345e300) myscale = 1.0;
 #endif
     QST(18)
 #define QP_PAN(J) panel_step<J, NW, CPL>(a, trow, myscale, diag, blk_live, c, g, wave, sh, tau_out); QST(19 + J)
-    QP_PAN(0) QP_PAN(1) QP_PAN(2) QP_PAN(3) QP_PAN(4) QP_PAN(5) QP_PAN(6) QP_PAN(7)
+    QP_PAN(0)
+    mid();
+    QP_PAN(1) QP_PAN(2) QP_PAN(3) QP_PAN(4) QP_PAN(5) QP_PAN(6) QP_PAN(7)
     QP_PAN(8) QP_PAN(9) QP_PAN(10) QP_PAN(11) QP_PAN(12) QP_PAN(13) QP_PAN(14) QP_PAN(15)
 #undef QP_PAN
+    return true;
+}
+
+// Two-launch form, first launch: one workgroup per chain selects and factors the panel and writes it out for qp_update_kernel.
+template <int NW, int CPL>
+__global__ __launch_bounds__(64 * NW) void qp_panel_kernel(Mat Am, QrWork w, int n, int k) {
+    __shared__ PanelShared<NW> sh;
+    const int chain = blockIdx.y;
+    double* __restrict__ A = Am.at(chain);
+    double* __restrict__ pw = w.pw + (long)chain * w.pw_stride;
+    const double* __restrict__ Y = pw;                         // [QP_SR][n]
+    double* __restrict__ Vp = pw + qp_off_vp(n) + (long)n * k;                    // [n][QP_B] column-major clean copy of THIS panel's reflectors
+    double* __restrict__ Tm = pw + qp_off_tm(n) + (long)QP_B * k;                 // [QP_B][QP_B] column-major, one per panel
+    double* __restrict__ VTp = pw + qp_off_vtp(n) + (long)n * k;                  // the same panel row-major ([n][QP_B]): the operand of V^T A is read along its rows
+    int* __restrict__ pivpos = w.pivpos + (long)chain * w.pivpos_stride;
+    double* tau = w.tau + (long)chain * w.tau_stride;
+    int* jpvt = w.jpvt + (long)chain * w.jpvt_stride;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int c = lane & 15, g = lane >> 4;
+
+#ifdef DQ_QP_STAMPS
+    __shared__ unsigned long long qst[40];
+#endif
+    double a[CPL][16], trow[QP_B], myscale;
+    unsigned diag; int mycol;
+    qp_factor_panel<NW, CPL>(A, Y, pivpos, n, k, sh, tau + k, a, trow, myscale, diag, mycol, [] { return false; }, [] {} QP_QST_ARG);
     // ---- write-out: R0 / beta / reflectors in place, the clean reflector panel (unit diagonal, zeros above), T, jpvt, pivpos ----
 #pragma unroll
     for (int b = 0; b < CPL; ++b) {
@@ -488,16 +530,15 @@ __global__ __launch_bounds__(64 * QP_UW) void qp_update_kernel(Mat Am, QrWork w,
     const int chain = blockIdx.y;
     double* __restrict__ pw = w.pw + (long)chain * w.pw_stride;
     if (UPDATE && (int)blockIdx.x >= q_first) {
-        qp_q_role<TPW>(red, pw + (long)(QP_SR + 2 * n) * n + (long)QP_B * n, Lm.at(chain), pw + (long)QP_SR * n + (long)n * k,
-                       pw + (long)QP_SR * n + (long)n * n + (long)QP_B * n + (long)n * k, pw + (long)QP_SR * n + (long)n * n + (long)QP_B * k, n, k,
-                       (int)blockIdx.x - q_first);
+        qp_q_role<TPW>(red, pw + qp_off_qacc(n), Lm.at(chain), pw + qp_off_vp(n) + (long)n * k, pw + qp_off_vtp(n) + (long)n * k,
+                       pw + qp_off_tm(n) + (long)QP_B * k, n, k, (int)blockIdx.x - q_first);
         return;
     }
     double* __restrict__ A = Am.at(chain);
     double* __restrict__ Y = pw;
-    const double* __restrict__ Vp = pw + (long)QP_SR * n + (long)n * k;
-    const double* __restrict__ Tm = pw + (long)QP_SR * n + (long)n * n + (long)QP_B * k;
-    const double* __restrict__ VTp = pw + (long)QP_SR * n + (long)n * n + (long)QP_B * n + (long)n * k;
+    const double* __restrict__ Vp = pw + qp_off_vp(n) + (long)n * k;
+    const double* __restrict__ Tm = pw + qp_off_tm(n) + (long)QP_B * k;
+    const double* __restrict__ VTp = pw + qp_off_vtp(n) + (long)n * k;
     int* __restrict__ pivpos = w.pivpos + (long)chain * w.pivpos_stride;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int r16 = lane & 15, kk = lane >> 4;
@@ -597,12 +638,266 @@ __global__ __launch_bounds__(64 * QP_UW) void qp_update_kernel(Mat Am, QrWork w,
     }
 }
 
+// ---- fused form: one launch per panel ----
+// Grid and roles as qp_update_kernel<true>'s, NW waves.  The panel's inputs (the sketch of parity k / 16, pivpos, rows >= k of the selected
+// columns) are visible to every workgroup when the launch starts and the factorisation is deterministic, so EVERY workgroup factors the
+// panel itself (qp_factor_panel: bit for bit what qp_panel_kernel computes), keeps the clean reflector panel and T in LDS and goes straight
+// on to its own column block: no panel launch, no reflector panels in global memory, no cold read-back, and no workgroup ever waits for
+// another.  What makes that safe in place -- nothing the factorisation reads may be written while some workgroup has yet to read it:
+//   sketch   two buffers: the step reads parity k / 16 and writes the other one;
+//   A        the update stores only to live columns, the factorisation gathers only the 16 selected ones, and a selected column counts
+//            as retired in every workgroup (sel[] in LDS);
+//   R0 / beta in place (rows k .. k + 15 of the selected columns, read by assemble_r_kernel), tau, jpvt, pivpos: written by the workgroup
+//            that draws the LAST ticket of the launch from the chain's counter.  A ticket is drawn after all global loads of the workgroup's
+//            factorisation have landed (past step 0 of the panel, consumed at the end: the round trip is hidden), so the last arriver knows
+//            that nobody will read those locations again in this launch; it holds the same values as everybody else, consumes nothing from the
+//            others (relaxed, no acquire), and the kernel boundary publishes its stores.  It also puts the counter back to zero.
+//            A column block whose 16 columns were retired by earlier panels draws its ticket at once and leaves -- unless it is the last.
+// The reflector tails below the diagonal of the selected columns are not written at all: Q is accumulated, nothing reads them.
+// Phase 2 keeps the update kernel's arithmetic: tile rt belongs to "virtual wave" rt % QP_UW, a wave carries the virtual waves wave, wave + NW,
+// ..., each with its own partial sums, and the cross-wave sums run over the QP_UW virtual waves in the same order -- bit-identical results.
+// V in LDS: one copy, column c at c * LDV with LDV odd: the operand of V^T A (16 lanes <-> 16 columns at one row) and the operand of V W' (16
+// lanes <-> 16 consecutive rows of one column) both hit 16 different banks.
+template <int NW, int CPL, int TPW>
+__global__ __launch_bounds__(64 * NW) void qp_step_kernel(Mat Am, QrWork w, int n, int k, Mat Lm, int q_first) {
+    constexpr int YT = QP_YT;
+    constexpr int NV = (QP_UW + NW - 1) / NW;                  // virtual waves per wave
+    constexpr int LDV = 64 * NW * CPL + 1;
+    __shared__ PanelShared<NW> sh;
+    __shared__ double Vs[QP_B * LDV];
+    __shared__ double Ts[QP_B * (QP_B + 1)];
+    __shared__ double red[QP_UW][YT * 4][64];
+    __shared__ double s_tau[QP_B];
+    __shared__ unsigned s_ticket;
+#ifdef DQ_QP_STAMPS
+    __shared__ unsigned long long qst[40];
+#endif
+    const int chain = blockIdx.y;
+    double* pw = w.pw + (long)chain * w.pw_stride;
+    const bool qrole = (int)blockIdx.x >= q_first;             // uniform per workgroup
+    const int cb = qrole ? (int)blockIdx.x - q_first : (int)blockIdx.x;
+    double* A = Am.at(chain);
+    const int par = (k / QP_B) & 1;
+    const double* __restrict__ Yr = pw + (long)par * QP_SR * n;
+    double* __restrict__ Yw = pw + (long)(par ^ 1) * QP_SR * n;
+    unsigned* counter = reinterpret_cast<unsigned*>(pw + qp_off_ticket(n));
+    int* pivpos = w.pivpos + (long)chain * w.pivpos_stride;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r16 = lane & 15, kk = lane >> 4;
+    const int col = 16 * cb + r16;
+    double* Xc = (qrole ? pw + qp_off_qacc(n) : A) + (long)n * col;     // my column of the trailing matrix | of Qacc
+    const int m_tiles = (n - k) / 16;
+    // the block's own tiles first: the loads overlap the factorisation instead of costing a dependent round after it.  (Issued behind the
+    // sketch they would not let the selection start any sooner: the loads sit under wave-uniform conditions, so the compiler cannot
+    // count them and waits for all of them before the first use of the sketch either way.)
+    const int pp_ld = pivpos[col];
+    d4 X[NV][TPW];
+#pragma unroll
+    for (int vi = 0; vi < NV; ++vi) {
+#pragma unroll
+        for (int ti = 0; ti < TPW; ++ti) {
+            const int vw = wave + NW * vi, rt = vw + QP_UW * ti;
+            X[vi][ti] = d4{0.0, 0.0, 0.0, 0.0};
+            if (vw < QP_UW && rt < m_tiles) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) X[vi][ti][r] = Xc[k + 16 * rt + kk + 4 * r];
+            }
+        }
+    }
+    const int pp = qrole ? -1 : pp_ld;
+    const unsigned last_ticket = gridDim.x - 1;
+    bool have_ticket = false;
+    unsigned ticket = 0u;
+    // ---- phase 1 ----
+    double a[CPL][16], trow[QP_B], myscale;
+    unsigned diag; int mycol;
+    const bool factored = qp_factor_panel<NW, CPL>(A, Yr, pivpos, n, k, sh, s_tau, a, trow, myscale, diag, mycol, [&] {
+        // the sketch loads are in flight beside the tiles': the retired test costs no round of its own
+        if (__ballot(pp < 0) != 0ULL) return false;            // every wave sees the same 16 columns: uniform
+        if (t == 0) s_ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        have_ticket = true;                                     // all 16 columns retired by earlier panels: nothing to update ...
+        return s_ticket != last_ticket;                         // ... but the last arriver has the write-out to do: it factors the panel for that alone
+    }, [&] {
+        if (!have_ticket && t == 0) {
+            // a zero offset in a vector register the compiler cannot see through: with a uniform address it turns the atomic into its
+            // wave-aggregated form (mbcnt / readfirstlane), which waits for the round trip on the spot instead of at the end of the panel
+            long off = 0;
+            asm volatile("" : "+v"(off));
+            ticket = __hip_atomic_fetch_add(counter + off, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    } QP_QST_ARG);
+    if (!factored) return;
+    const int c = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int b = 0; b < CPL; ++b) {                            // the clean reflector panel: unit diagonal, zeros above
+        const int r0 = 64 * NW * b + 64 * wave + 16 * g;
+        if (r0 >= k && r0 < n) {
+            const bool isd = (diag >> b) & 1u;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const bool below = !isd || i > c;
+                Vs[c * LDV + r0 + i] = below ? a[b][i] * myscale : (i == c ? 1.0 : 0.0);
+            }
+        }
+    }
+    if (wave == 0 && g == 0) {
+#pragma unroll
+        for (int i = 0; i < QP_B; ++i) Ts[c + (QP_B + 1) * i] = trow[i];
+    }
+    if (!have_ticket && t == 0) s_ticket = ticket;
+    __syncthreads();
+    QST(35)
+    if (s_ticket == last_ticket) {                             // uniform: everybody else has read what this overwrites
+        double* tau = w.tau + (long)chain * w.tau_stride;
+        int* jpvt = w.jpvt + (long)chain * w.jpvt_stride;
+#pragma unroll
+        for (int b = 0; b < CPL; ++b) {
+            if ((diag >> b) & 1u) {                             // this lane holds rows k .. k + 15 of column mycol
+#pragma unroll
+                for (int i = 0; i < 16; ++i) if (i <= c) A[(long)n * mycol + k + i] = a[b][i];
+            }
+        }
+        if (wave == 0 && g == 0) { jpvt[k + c] = mycol; pivpos[mycol] = k + c; tau[k + c] = s_tau[c]; }
+        if (t == 0) *counter = 0u;
+        if (have_ticket) return;
+    }
+    QST(36)
+    // ---- phase 2: qp_update_kernel<true> / qp_q_role with V and T from LDS ----
+    bool sel_hit = false;
+#pragma unroll
+    for (int j = 0; j < QP_B; ++j) sel_hit |= sh.sel[j] == col;
+    const bool live_col = qrole || (pp < 0 && !sel_hit);
+    double tv[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) tv[s] = Ts[(kk + 4 * s) + (QP_B + 1) * r16];
+    const bool first = qrole && k == 0;                        // before the first factor the accumulator is the identity: a select, no branch
+#pragma unroll
+    for (int vi = 0; vi < NV; ++vi)
+#pragma unroll
+        for (int ti = 0; ti < TPW; ++ti)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) X[vi][ti][r] = first ? ((16 * (wave + NW * vi + QP_UW * ti) + kk + 4 * r == col) ? 1.0 : 0.0) : X[vi][ti][r];
+#pragma unroll
+    for (int vi = 0; vi < NV; ++vi) {
+        const int vw = wave + NW * vi;
+        if (vw < QP_UW) {
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int ti = 0; ti < TPW; ++ti) {
+                const int rt = vw + QP_UW * ti;
+                if (rt < m_tiles) {
+                    const double* vrow = Vs + r16 * LDV + (k + 16 * rt + kk);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vrow[4 * s], X[vi][ti][s], acc, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[vw][r][lane] = acc[r];
+        }
+    }
+    __syncthreads();
+    d4 W;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double v = red[0][r][lane];
+#pragma unroll
+        for (int q = 1; q < QP_UW; ++q) v += red[q][r][lane];
+        W[r] = live_col ? v : 0.0;
+    }
+    d4 wp = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) wp = __builtin_amdgcn_mfma_f64_16x16x4f64(tv[s], W[s], wp, 0, 0, 0);
+    wp = -wp;
+    __syncthreads();
+    QST(37)
+    double* L = Lm.at(chain);
+#pragma unroll
+    for (int vi = 0; vi < NV; ++vi) {
+        const int vw = wave + NW * vi;
+        if (vw < QP_UW) {
+            d4 ya[YT];
+#pragma unroll
+            for (int yt = 0; yt < YT; ++yt) ya[yt] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int ti = 0; ti < TPW; ++ti) {
+                const int rt = vw + QP_UW * ti;
+                if (rt < m_tiles) {
+                    const int r0 = k + 16 * rt;
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) X[vi][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(Vs[(kk + 4 * s) * LDV + r0 + r16], wp[s], X[vi][ti], 0, 0, 0);
+                    if (qrole) {
+                        if (rt == 0) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) L[(long)n * (k + kk + 4 * r) + col] = X[vi][ti][r];     // Q[col][k + kk + 4 r] = Q^T[k + kk + 4 r][col]
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) Xc[r0 + kk + 4 * r] = X[vi][ti][r];
+                        }
+                    } else {
+                        if (live_col) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) Xc[r0 + kk + 4 * r] = X[vi][ti][r];
+                        }
+                        if (rt >= 1) {                             // rows of the NEXT trailing matrix: sketch them while they are in registers
+#pragma unroll
+                            for (int s = 0; s < 4; ++s) {
+                                const unsigned bits = qp_row_bits((unsigned)(r0 + kk + 4 * s));
+#pragma unroll
+                                for (int yt = 0; yt < YT; ++yt) ya[yt] = __builtin_amdgcn_mfma_f64_16x16x4f64(qp_sign(bits, 16 * yt + r16), X[vi][ti][s], ya[yt], 0, 0, 0);
+                            }
+                        }
+                    }
+                }
+            }
+            if (!qrole) {
+#pragma unroll
+                for (int yt = 0; yt < YT; ++yt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) red[vw][4 * yt + r][lane] = ya[yt][r];
+            }
+        }
+    }
+    if (qrole) return;
+    __syncthreads();
+    for (int idx = t; idx < YT * 4 * 64; idx += 64 * NW) {
+        const int l = idx & 63, q = idx >> 6, yt = q >> 2, r = q & 3;
+        double v = red[0][q][l];
+#pragma unroll
+        for (int qq = 1; qq < QP_UW; ++qq) v += red[qq][q][l];
+        Yw[(long)(16 * yt + (l >> 4) + 4 * r) * n + 16 * cb + (l & 15)] = v;
+    }
+#ifdef DQ_QP_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    QST(38)
+    __syncthreads();
+    if (t == 0 && (k == 0 || k == n / 2) && blockIdx.x == 0 && blockIdx.y == 0) {
+        printf("step k=%d n=%d (100 MHz ticks): loads %llu | sel steps", k, n, qst[1] - qst[0]);
+        for (int j = 0; j < 16; ++j) printf(" %llu", qst[2 + j] - qst[1 + j]);
+        printf(" | gather %llu | panel steps", qst[18] - qst[17]);
+        for (int j = 0; j < 16; ++j) printf(" %llu", qst[19 + j] - qst[18 + j]);
+        printf(" | deposit + ticket %llu | last arriver %llu | W %llu | update + sketch %llu | total %llu\n", qst[35] - qst[34], qst[36] - qst[35],
+               qst[37] - qst[36], qst[38] - qst[37], qst[38] - qst[0]);
+    }
+#endif
+}
+
+// the fused step keeps a whole reflector panel in LDS and a wave's tiles in registers: instances up to n = 576 (<3, 3>)
+bool qr_panel_fused_fits(int n) { return n <= 576; }
+// ... and where it is shorter than the pair it replaces (kernel durations, us: 24.4 against 19.9 + 5.3 at n = 64, 25.4 against 21.3 + 5.3 at 128, 29.6
+// against 25.2 + 6.5 at 256, 40.9 against 35.1 + 9.2 at 384 / 512).  Not at n = 576: three waves do the update of 36 row tiles that eight waves
+// do in the two-launch form, 50.2 against 39.2 + 10.4 us, and a cfg-5 sweep is 2.5 ms slower with it
+bool qr_panel_fused_default(int n) { return n <= 512; }
+// two_launch: the workspace also holds the reflector panels and T factors that qp_panel_kernel hands to qp_update_kernel
+long qr_panel_work_doubles(int n, bool two_launch) { return two_launch ? qp_off_vtp(n) + (long)n * n : qp_off_vp(n); }
 // argument guard of launch_qr_panel: n a multiple of 16 in [16, 1024] and the workspace present
-static bool qr_panel_ok(int n, const QrWork& w) { return n >= 16 && n <= 1024 && n % 16 == 0 && w.pw != nullptr && w.pivpos != nullptr && w.pw_stride >= qr_panel_work_doubles(n); }
-long qr_panel_work_doubles(int n) { return (long)(QP_SR + 3 * n) * n + (long)QP_B * n; }   // Y | V panels | T factors | V panels row-major | Qacc
+static bool qr_panel_ok(int n, const QrWork& w, bool two_launch) {
+    return n >= 16 && n <= 1024 && n % 16 == 0 && w.pw != nullptr && w.pivpos != nullptr && w.pw_stride >= qr_panel_work_doubles(n, two_launch);
+}
 
 int launch_qr_panel(Mat A, Mat L, QrWork w, int n, int n_chains, hipStream_t s) {
-    if (!qr_panel_ok(n, w)) { set_error("panel QR: n must be a multiple of 16 in [16, 1024] and the workspace present"); return -1; }
+    const bool fused = !w.pw_two_launch && qr_panel_fused_fits(n);
+    if (!qr_panel_ok(n, w, !fused)) { set_error("panel QR: n must be a multiple of 16 in [16, 1024] and the workspace present"); return -1; }
     const int nb = n / 16;
     const int tpw = (nb + QP_UW - 1) / QP_UW;
     // GRID column blocks, of which those from QFIRST on have the Q role
@@ -610,14 +905,22 @@ int launch_qr_panel(Mat A, Mat L, QrWork w, int n, int n_chains, hipStream_t s) 
                           if (tpw <= 2) hipLaunchKernelGGL((qp_update_kernel<U, 2>), ugrid, dim3(64 * QP_UW), 0, s, A, w, n, K, L, QFIRST); \
                           else if (tpw <= 5) hipLaunchKernelGGL((qp_update_kernel<U, 5>), ugrid, dim3(64 * QP_UW), 0, s, A, w, n, K, L, QFIRST); \
                           else hipLaunchKernelGGL((qp_update_kernel<U, 8>), ugrid, dim3(64 * QP_UW), 0, s, A, w, n, K, L, QFIRST); } while (0)
-    QP_UPD(false, 0, nb, nb);
+    QP_UPD(false, 0, nb, nb);                                      // pivpos = -1 and the sketch of A (parity 0)
     for (int k = 0; k < n; k += QP_B) {
+        const bool trailing = k + QP_B < n;                        // the last panel has no trailing matrix: its factor goes into Q alone
+        const int grid = trailing ? 2 * nb : nb, q_first = trailing ? nb : 0;   // trailing update | Q accumulation
+        if (fused) {
+#define QP_STEP(NW, CPL, TPW) hipLaunchKernelGGL((qp_step_kernel<NW, CPL, TPW>), dim3(grid, n_chains), dim3(64 * NW), 0, s, A, w, n, k, L, q_first)
+            if (n <= 64) QP_STEP(1, 1, 1); else if (n <= 128) QP_STEP(2, 1, 1); else if (n <= 256) QP_STEP(4, 1, 2); else if (n <= 512) QP_STEP(4, 2, 4);
+            else QP_STEP(3, 3, 5);
+#undef QP_STEP
+            continue;
+        }
 #define QP_LAUNCH(NW, CPL) hipLaunchKernelGGL((qp_panel_kernel<NW, CPL>), dim3(1, n_chains), dim3(64 * NW), 0, s, A, w, n, k)
         if (n <= 64) QP_LAUNCH(1, 1); else if (n <= 128) QP_LAUNCH(2, 1); else if (n <= 256) QP_LAUNCH(4, 1); else if (n <= 512) QP_LAUNCH(4, 2);
         else if (n <= 576) QP_LAUNCH(3, 3); else if (n <= 768) QP_LAUNCH(4, 3); else QP_LAUNCH(4, 4);
 #undef QP_LAUNCH
-        if (k + QP_B < n) QP_UPD(true, k, 2 * nb, nb);             // trailing update | Q accumulation
-        else QP_UPD(true, k, nb, 0);                               // the last panel has no trailing matrix: its factor goes into Q alone
+        QP_UPD(true, k, grid, q_first);
     }
 #undef QP_UPD
     DQ_HIP(hipGetLastError());
