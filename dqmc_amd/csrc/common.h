@@ -168,10 +168,14 @@ int launch_tri_solve(CMat R, const int* perm, long perm_stride, Mat X, CVec dg, 
 
 // ---- lu_gj.hip ----------------------------------------------------------------
 // X = A^-1 B for n <= 1024 by blocked Gauss-Jordan elimination with partial pivoting (no substitution phase); A and B
-// are destroyed.  SA: n*n scratch per chain, tinv: 2048 doubles per chain, perm / rowpos: n ints per chain.
+// are destroyed.  SA: n*n scratch per chain, tinv: 2048 doubles per chain, perm / rowpos / rowpos_alt: n ints per chain.
 // logabsdet (optional): (+)= log|det A|.  *info |= DQ_STATUS_PIVOT on a zero / NaN pivot.
-int launch_gj_solve(Mat A, Mat B, Mat X, Mat SA, double* tinv, int* perm, long perm_stride, int* rowpos, long rowpos_stride,
-                    double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, hipStream_t s);
+// fused: one launch per panel (gj_step_kernel: every update workgroup factors the panel) where gj_fused_fits(n); rowpos and rowpos_alt
+// then alternate with the panel's parity.  Both forms give the same bits.
+bool gj_fused_fits(int n);                   // the one-launch-per-panel form has an instance for this n
+bool gj_fused_default(int n);                // ... and is what the solves use at this n unless DQMC_GJ_FUSED says otherwise
+int launch_gj_solve(Mat A, Mat B, Mat X, Mat SA, double* tinv, int* perm, long perm_stride, int* rowpos, int* rowpos_alt, long rowpos_stride,
+                    double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, bool fused, hipStream_t s);
 
 // ---- update.hip ---------------------------------------------------------------
 struct UpdateTables {            // per chain, 64 doubles: model constants the slice kernel needs

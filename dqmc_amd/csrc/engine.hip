@@ -40,12 +40,13 @@ int init_device_kernels(int device) {
 // Kernel families of to_LDR, the solves and the local update, decided here and nowhere else (the per-size instance inside a family
 // is chosen next to its kernel) from n, the chain count, the CU reservation and the switches (README.md, "Environment switches").
 // ---------------------------------------------------------------------------
-struct Switches { bool qr_panel; int qr_panel_fused; bool qr_streaming, walk_submatrix, lu_classic, slice_multikernel; };
+struct Switches { bool qr_panel; int qr_panel_fused, gj_fused; bool qr_streaming, walk_submatrix, lu_classic, slice_multikernel; };
 static const Switches& switches() {           // read once per process
     static const Switches sw = [] {
         const char* panel = getenv("DQMC_QR_PANEL");
         const char* fused = getenv("DQMC_QR_PANEL_FUSED");          // unset (-1): where it measured faster; 0: nowhere; 1: wherever an instance exists
-        return Switches{!(panel && atoi(panel) == 0), fused ? (atoi(fused) != 0 ? 1 : 0) : -1, getenv("DQMC_QR_STREAMING") != nullptr, getenv("DQMC_WALK_SUBMATRIX") != nullptr,
+        const char* gj = getenv("DQMC_GJ_FUSED");                   // the same three states for the Gauss-Jordan solve (lu_gj.hip)
+        return Switches{!(panel && atoi(panel) == 0), fused ? (atoi(fused) != 0 ? 1 : 0) : -1, gj ? (atoi(gj) != 0 ? 1 : 0) : -1, getenv("DQMC_QR_STREAMING") != nullptr, getenv("DQMC_WALK_SUBMATRIX") != nullptr,
                         getenv("DQMC_LU_CLASSIC") != nullptr, getenv("DQMC_SLICE_MULTIKERNEL") != nullptr};
     }();
     return sw;
@@ -141,11 +142,12 @@ struct Ctx {
     static constexpr int NT = 6, NV = 5;       // matrices T0 .. T4 and the Gauss-Jordan scratch T5; vectors V0 .. V3 and the QR tau V4
     DevPtr<double> pool;                       // NT * C * nn
     DevPtr<double> vpool;                      // NV * C * n
-    DevPtr<int> ipool;                         // 3 * C * n ints + info
+    DevPtr<int> ipool;                         // 4 * C * n ints + info
     DevPtr<unsigned long long> qsync;          // cooperative QRCP records
     DevPtr<int> qabort;                        // cooperative QRCP abort words: C
     DevPtr<double> tinv;                       // Gauss-Jordan panel inverses: 2048 * C
     DevPtr<double> qpw;                        // panel-pivoted QR (qr_panel.hip): qr_panel_work_doubles(n, qpw_two_launch) * C, zeroed (the ticket counters)
+    bool gj_fused = false;                     // the Gauss-Jordan solve takes one launch per panel (gj_step_kernel): where it measured faster, or DQMC_GJ_FUSED
     bool qpw_two_launch = false;               // ... in the two-launch form (panel kernel + update kernel): sizes the fused step is not used at, or DQMC_QR_PANEL_FUSED=0
     DevPtr<int> qpivpos;                       // ... and its pivot positions: n * C
     DevPtr<double> trinv;                      // blocked triangular solve: inverses of the 16 x 16 diagonal blocks, 16 * (n + 16) * C
@@ -156,7 +158,8 @@ struct Ctx {
     int* jpvt() const { return ipool.get(); }
     int* lperm() const { return ipool.get() + (long)C * n; }
     int* rowpos() const { return ipool.get() + 2L * C * n; }
-    int* info() const { return ipool.get() + 3L * C * n; }
+    int* rowpos_alt() const { return ipool.get() + 3L * C * n; }       // the fused Gauss-Jordan step alternates between the two
+    int* info() const { return ipool.get() + 4L * C * n; }
 
     int init(int n_, int C_, int device_) {
         n = n_; C = C_; device = device_; nn = (long)n * n;
@@ -165,7 +168,7 @@ struct Ctx {
         DQ_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         DQ_TRY(dev_alloc(pool, (size_t)NT * C * nn));
         DQ_TRY(dev_alloc(vpool, (size_t)NV * C * n));
-        DQ_TRY(dev_alloc(ipool, 3L * C * n + 4));
+        DQ_TRY(dev_alloc(ipool, 4L * C * n + 4));
         plan = KernelPlan::pick(n, C);
         if (plan.qr == QrFamily::Cooperative) { DQ_TRY(dev_alloc(qsync, (size_t)qrcp_coop_sync_granules(n) * C)); DQ_TRY(dev_alloc(qabort, C)); }
         if (plan.qr == QrFamily::Panel) {
@@ -175,9 +178,13 @@ struct Ctx {
             DQ_TRY(dev_alloc(qpw, qpw_count)); DQ_TRY(dev_alloc(qpivpos, (size_t)n * C));
             DQ_HIP(hipMemsetAsync(qpw.get(), 0, sizeof(double) * qpw_count, stream));
         }
-        if (plan.solve == KernelPlan::Solve::GaussJordan) DQ_TRY(dev_alloc(tinv, (size_t)2048 * C));
+        if (plan.solve == KernelPlan::Solve::GaussJordan) {
+            DQ_TRY(dev_alloc(tinv, (size_t)2048 * C));
+            const int fused = switches().gj_fused;
+            gj_fused = fused < 0 ? gj_fused_default(n) : fused == 1 && gj_fused_fits(n);
+        }
         if (plan.rinv == KernelPlan::Rinv::Blocked) DQ_TRY(dev_alloc(trinv, (size_t)16 * (n + 16) * C));
-        DQ_HIP(hipMemsetAsync(ipool.get(), 0, sizeof(int) * (3L * C * n + 4), stream));
+        DQ_HIP(hipMemsetAsync(ipool.get(), 0, sizeof(int) * (4L * C * n + 4), stream));
         return 0;
     }
     ~Ctx() { if (stream) (void)hipStreamDestroy(stream); }
@@ -247,7 +254,7 @@ struct Ctx {
     // Returns the matrix holding Y in *Y.  M and RHS are destroyed.  (uses T5 as scratch)
     int solve(Mat M, Mat RHS, Mat out, double* logdet_acc, Mat* Y) {
         if (plan.solve == KernelPlan::Solve::GaussJordan) {
-            DQ_TRY(launch_gj_solve(M, RHS, out, T(5), tinv.get(), lperm(), n, rowpos(), n, logdet_acc, 1, info(), n, C, stream));
+            DQ_TRY(launch_gj_solve(M, RHS, out, T(5), tinv.get(), lperm(), n, rowpos(), rowpos_alt(), n, logdet_acc, 1, info(), n, C, gj_fused, stream));
             *Y = out; return 0;
         }
         DQ_TRY(launch_lu_blocked(M, lperm(), n, rowpos(), n, logdet_acc, 1, info(), n, C, stream));

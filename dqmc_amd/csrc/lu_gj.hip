@@ -25,6 +25,10 @@
 // (measured on the cfg-3 stabilisation matrices, cond(M) ~ 1e3: 1e-13 .. 9e-13 on G, the same
 // spread two LAPACK routes show among themselves).  For n = 256: 8 x (panel 13 us + update
 // 8 us) instead of the 8 x (30 + 18 + 7) us of lu_blocked.hip plus a ~200 us substitution.
+//
+//   gj_step_kernel    (64 < n <= 256, the default for 128 < n <= 256) the two in ONE launch per panel: the update's grid, every workgroup of which factors the panel itself
+//                     with the panel kernel's device functions and keeps the pivot block, its inverses, perm and the new rowpos in LDS; the
+//                     same bits as the two launches (DQMC_GJ_FUSED=0 keeps those; tests/test_gpu_fused_gj.py).
 #include "common.h"
 #include "wave.h"
 #include <cstdlib>
@@ -204,7 +208,8 @@ __device__ __forceinline__ void gj_tri_steps(double (&x)[16], const double* T0, 
     };
     (step(std::integral_constant<int, Js>{}), ...);
 }
-__device__ __forceinline__ void gj_panel_tri_inverses(double (&LU)[GJ_NB][GJ_NB], double* tinv, int lane) {
+// inv: 4 x (16 x 16) column-major, in global memory or in LDS
+__device__ __forceinline__ void gj_panel_tri_inverses(double (&LU)[GJ_NB][GJ_NB], double* inv, int lane) {
     // one column per lane (lane = 16 * block + column): unit-lower blocks by forward substitution, upper blocks by the same recurrence on
     // the index-reversed block
     const int blk = lane >> 4, c = lane & 15;
@@ -216,7 +221,7 @@ __device__ __forceinline__ void gj_panel_tri_inverses(double (&LU)[GJ_NB][GJ_NB]
     const double rd = 1.0 / LU[lane & 31][lane & 31];
     double x[16];
     gj_tri_steps(x, T0, sg, cc, up, (blk & 1) != 0, rd, std::make_integer_sequence<int, 16>{});
-    double* out = tinv + GJ_NB * GJ_NB + 256 * blk + 16 * c;
+    double* out = inv + 256 * blk + 16 * c;
 #pragma unroll
     for (int j = 0; j < 16; ++j) out[up ? 15 - j : j] = x[j];
 }
@@ -336,15 +341,101 @@ struct GjStepsMW<GJ_NB, NW, RPL> {
 // NW waves (the most the workgroup may have), RPL matrix rows per lane: row t + 64 NW q is slot q of thread t.  One wave per SIMD up to n = 768
 // (<4, 1> n <= 256, <4, 2> <= 512, <3, 3> <= 576, <4, 3> <= 768), two beyond (<8, 2>): with one row per lane n = 576 took 9 waves, three on
 // a SIMD, and a step cost what the three issue one after the other plus nine single-lane row publishes instead of three.
+//
+// The panel is three device functions, shared by gj_panel_mw_kernel (one workgroup per chain, results to global memory) and
+// gj_step_kernel (every update workgroup factors the panel itself and keeps the results in LDS): the same code, hence the same pivots.
+template <int NW, int RPL>
+struct GjPanelShared {
+    double LU[GJ_NB][GJ_NB];
+    double slot_row[2][NW][GJ_NB + 2];                   // row | reciprocal of its pivot element
+    unsigned long long slot_key[2][(NW + 1) & ~1];
+    int s_sing;
+};
+// The live rows of the panel's columns into registers.  oldpos: the row's rowpos entry before this panel (-1 = live).  CLAMPED: every load
+// has a valid, clamped address and is masked at use, so that the row loads do not wait for rowpos (the fused step, where the rows of a
+// panel are read by every workgroup anyway); otherwise only live rows are loaded, behind rowpos (the panel kernel, as it always did).
+template <int NW, int RPL, bool CLAMPED>
+__device__ __forceinline__ void gj_panel_load(const double* __restrict__ A, const int* rowpos, int n, int k0, int nbw, int t, double (&a)[RPL][GJ_NB], unsigned& live,
+                                              int (&oldpos)[RPL]) {
+    live = 0u;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = t + 64 * NW * q;
+        const int rc = r < n ? r : 0;
+        if (CLAMPED) {
+            double v[GJ_NB];
+#pragma unroll
+            for (int c = 0; c < GJ_NB; ++c) v[c] = A[rc + (long)n * (k0 + (c < nbw ? c : 0))];
+            oldpos[q] = k0 == 0 ? -1 : rowpos[rc];
+            const bool lv = r < n && oldpos[q] < 0;
+            live |= lv ? (1u << q) : 0u;
+#pragma unroll
+            for (int c = 0; c < GJ_NB; ++c) a[q][c] = (lv && c < nbw) ? v[c] : 0.0;
+        } else {
+            oldpos[q] = k0 == 0 ? -1 : rowpos[rc];
+            const bool lv = r < n && oldpos[q] < 0;
+            live |= lv ? (1u << q) : 0u;
+#pragma unroll
+            for (int c = 0; c < GJ_NB; ++c) a[q][c] = (lv && c < nbw) ? A[r + (long)n * (k0 + c)] : 0.0;
+        }
+    }
+}
+// The elimination steps, then the pivot block into sh.LU (row-major in pivot order, identity beyond nbw) and the singular flag into
+// sh.s_sing: both are complete after the caller's next barrier.  mypos[q]: the pivot position row q of this thread took in this panel, or -1;
+// myperm (wave 0, lane j): the row that became pivot j.
+template <int NW, int RPL>
+__device__ __forceinline__ void gj_panel_factor(GjPanelShared<NW, RPL>& sh, double (&a)[RPL][GJ_NB], unsigned& live, int (&mypos)[RPL], int& myperm, int t, int nbw, int k0
+#ifdef DQ_GJ_STAMPS
+                                                , unsigned long long& gstart, unsigned long long& gsteps_end
+#endif
+                                                ) {
+    constexpr int NWK = (NW + 1) & ~1;
+    static_assert(RPL <= 4, "two key bits name the slot");
+    const int lane = t & 63, wave = t >> 6;
+    bool singular = false;
+    myperm = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) mypos[q] = -1;
+    for (int e = t; e < GJ_NB * GJ_NB; e += blockDim.x) (&sh.LU[0][0])[e] = ((e >> 5) == (e & 31)) ? 1.0 : 0.0;   // identity padding for nbw < 32
+    if (t == 0) sh.s_sing = 0;
+    if (t < 2 * NWK) (&sh.slot_key[0][0])[t] = 0ULL;      // waves that do not exist never publish: their keys stay "no candidate"
+    lds_wait();
+    __builtin_amdgcn_s_barrier();                        // LDS only: loads the caller has in flight stay in flight
+    asm volatile("" ::: "memory");
+
+#ifdef DQ_GJ_STAMPS
+    unsigned long long gst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gprev;
+    asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gprev) :: "memory"); gstart = gprev;
+#endif
+    GjStepsMW<0, NW, RPL>::run(a, live, mypos, myperm, singular, lane, wave, nbw, k0, sh.slot_row, sh.slot_key GST_PASS);
+#ifdef DQ_GJ_STAMPS
+    gsteps_end = gprev;
+    if (t == 0 && k0 == 0 && blockIdx.x == 0 && blockIdx.y == 0)
+        printf("gj panel k0=0 grid.x=%d, %d waves x %d rows per lane, clocks over %d steps (each segment includes one stamp, ~130): (loop) %llu | search %llu | publish %llu | barrier %llu | keys %llu | row %llu | fma %llu | total %llu\n",
+               (int)gridDim.x, (int)(blockDim.x >> 6), RPL, nbw, gst[0], gst[1], gst[2], gst[3], gst[4], gst[5], gst[6], gprev - gstart);
+#endif
+
+    lds_wait();
+    __builtin_amdgcn_s_barrier();                        // identity fill done everywhere before the pivot rows overwrite theirs
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        if (mypos[q] >= 0) {
+            double* dst = &sh.LU[mypos[q] - k0][0];
+#pragma unroll
+            for (int c = 0; c < GJ_NB; c += 2) *reinterpret_cast<double2*>(dst + c) = make_double2(a[q][c], a[q][c + 1]);
+        }
+    }
+    if (singular && lane == 0) sh.s_sing = 1;
+}
+#ifdef DQ_GJ_STAMPS
+#define GJ_STAMP_VM(x) asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(x) :: "memory")
+#endif
+
 template <int NW, int RPL>
 __global__ __launch_bounds__(64 * NW) void gj_panel_mw_kernel(CMat Am, int* rowpos_p, long rowpos_stride, int* perm_p, long perm_stride, double* tinv_p,
                                                           double* logabsdet, int accumulate, int* info, int n, int k0) {
-    constexpr int NWK = (NW + 1) & ~1;
-    __shared__ __attribute__((aligned(16))) double LU[GJ_NB][GJ_NB];
-    __shared__ __attribute__((aligned(16))) double slot_row[2][NW][GJ_NB + 2];     // row | reciprocal of its pivot element
-    __shared__ __attribute__((aligned(16))) unsigned long long slot_key[2][NWK];
-    __shared__ int s_sing;
-    static_assert(RPL <= 4, "two key bits name the slot");
+    __shared__ __attribute__((aligned(16))) GjPanelShared<NW, RPL> sh;
     const int chain = blockIdx.y;
     const double* __restrict__ A = Am.at(chain);
     int* rowpos = rowpos_p + (long)chain * rowpos_stride;
@@ -352,62 +443,36 @@ __global__ __launch_bounds__(64 * NW) void gj_panel_mw_kernel(CMat Am, int* rowp
     double* tinv = tinv_p + (long)chain * 2 * GJ_NB * GJ_NB;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
 #ifdef DQ_GJ_STAMPS
-    unsigned long long gentry;
+    unsigned long long gentry, gstart, gprev;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gentry) :: "memory");
 #endif
     const int nbw = min(GJ_NB, n - k0);
-    unsigned live = 0u;
-    int mypos[RPL], myperm = 0; bool singular = false;
+    unsigned live;
+    int oldpos[RPL], mypos[RPL], myperm;
     double a[RPL][GJ_NB];
-#pragma unroll
-    for (int q = 0; q < RPL; ++q) {
-        const int r = t + 64 * NW * q;
-        const bool lv = r < n && (k0 == 0 ? true : rowpos[r < n ? r : 0] < 0);
-        live |= lv ? (1u << q) : 0u;
-        mypos[q] = -1;
-#pragma unroll
-        for (int c = 0; c < GJ_NB; ++c) a[q][c] = (lv && c < nbw) ? A[r + (long)n * (k0 + c)] : 0.0;
-    }
-    for (int e = t; e < GJ_NB * GJ_NB; e += blockDim.x) (&LU[0][0])[e] = ((e >> 5) == (e & 31)) ? 1.0 : 0.0;   // identity padding for nbw < 32
-    if (t == 0) s_sing = 0;
-    if (t < 2 * NWK) (&slot_key[0][0])[t] = 0ULL;         // waves that do not exist never publish: their keys stay "no candidate"
-    __syncthreads();
-
+    gj_panel_load<NW, RPL, false>(A, rowpos, n, k0, nbw, t, a, live, oldpos);
 #ifdef DQ_GJ_STAMPS
-    unsigned long long gst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gprev, gstart;
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gprev) :: "memory"); gstart = gprev;
+    gj_panel_factor<NW, RPL>(sh, a, live, mypos, myperm, t, nbw, k0, gstart, gprev);
+#else
+    gj_panel_factor<NW, RPL>(sh, a, live, mypos, myperm, t, nbw, k0);
 #endif
-    GjStepsMW<0, NW, RPL>::run(a, live, mypos, myperm, singular, lane, wave, nbw, k0, slot_row, slot_key GST_PASS);
-#ifdef DQ_GJ_STAMPS
-    if (t == 0 && k0 == 0 && blockIdx.y == 0)
-        printf("gj panel k0=0 n=%d, %d waves x %d rows per lane, clocks over %d steps (each segment includes one stamp, ~130): (loop) %llu | search %llu | publish %llu | barrier %llu | keys %llu | row %llu | fma %llu | total %llu\n",
-               n, (int)(blockDim.x >> 6), RPL, nbw, gst[0], gst[1], gst[2], gst[3], gst[4], gst[5], gst[6], gprev - gstart);
-#endif
-
-    __syncthreads();                                     // identity fill done everywhere before the pivot rows overwrite theirs
 #pragma unroll
     for (int q = 0; q < RPL; ++q) {
         const int r = t + 64 * NW * q;
         if (r < n) { if (k0 == 0) rowpos[r] = mypos[q]; else if (mypos[q] >= 0) rowpos[r] = mypos[q]; }
-        if (mypos[q] >= 0) {
-            double* dst = &LU[mypos[q] - k0][0];
-#pragma unroll
-            for (int c = 0; c < GJ_NB; c += 2) *reinterpret_cast<double2*>(dst + c) = make_double2(a[q][c], a[q][c + 1]);
-        }
     }
     if (wave == 0 && lane < nbw) perm[k0 + lane] = myperm;
-    if (singular && lane == 0) s_sing = 1;
     __syncthreads();
-    for (int e = t; e < GJ_NB * GJ_NB; e += blockDim.x) tinv[e] = (&LU[0][0])[e];
+    for (int e = t; e < GJ_NB * GJ_NB; e += blockDim.x) tinv[e] = (&sh.LU[0][0])[e];
 #ifdef DQ_GJ_STAMPS
     unsigned long long gmid;
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gmid) :: "memory");
+    GJ_STAMP_VM(gmid);
 #endif
-    if (wave == 0) gj_panel_tri_inverses(LU, tinv, lane);
-    else if (wave == 1) gj_panel_logdet(LU, logabsdet, accumulate, info, chain, lane, nbw, k0, s_sing);
+    if (wave == 0) gj_panel_tri_inverses(sh.LU, tinv + GJ_NB * GJ_NB, lane);
+    else if (wave == 1) gj_panel_logdet(sh.LU, logabsdet, accumulate, info, chain, lane, nbw, k0, sh.s_sing);
 #ifdef DQ_GJ_STAMPS
     unsigned long long gend;
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gend) :: "memory");
+    GJ_STAMP_VM(gend);
     if (t == 0 && k0 == 0 && blockIdx.y == 0) printf("   prologue %llu | steps %llu | LU hand-over (+ printf) %llu | epilogue %llu\n", gstart - gentry, gprev - gstart, gmid - gprev, gend - gmid);
 #endif
 }
@@ -535,11 +600,204 @@ __global__ __launch_bounds__(256) void gj_update_kernel(Mat Am, Mat Bm, Mat SAm,
         if (st_ok[reg]) dst[row0 + kk + 4 * reg + coff] = cold[reg] - acc[reg];
 }
 
+// One launch per panel: gj_update_kernel's grid and tile assignment, but every workgroup first factors the panel itself (the device
+// functions of gj_panel_mw_kernel: same code, same pivots) and keeps the pivot block, its triangular inverses, the panel's perm and the
+// new rowpos in LDS.  Nothing is handed over between workgroups and none waits for another.  The arithmetic of the update is
+// gj_update_kernel's bit for bit: operand partition k = 16h + 4s + kk, the order of the six substitution products, cold - acc.
+//
+// Within one launch every workgroup reads, and none writes:
+//   - the panel's columns A[:, k0 .. k0+31] (the trailing tiles start at column k0 + nbw) and SA[0 .. k0, panel] of the retired rows;
+//   - the pivot rows of this panel in the trailing columns of A and in B (st_ok masks them with the workgroup's own new rowpos);
+//   - rowpos of the previous panel: the new one goes to the OTHER half of the buffer (halves alternate with the panel's parity), written by
+//     workgroup 0 of the chain, which also performs the two read-modify-writes, logabsdet[chain] and the singular-pivot flag.
+// The writer row tile writes rows k0 .. k0+31 of SA / X, disjoint from the retired rows [0, k0) the S tiles update.
+// mult[][] and cold[] depend on no pivot: their loads are issued before the elimination steps, behind the panel's own in program order, so the
+// counted wait in front of the first step covers the panel's loads only; they have clamped addresses and are masked at use.
+template <int NW, int RPL>
+__global__ __launch_bounds__(64 * NW) void gj_step_kernel(Mat Am, Mat Bm, Mat SAm, Mat Xm, const int* rowpos_old_p, int* rowpos_new_p, long rowpos_stride,
+                                                          double* logabsdet, int accumulate, int* info, int n, int k0, int nA, int nS, int nCA) {
+    static_assert(NW == 4, "the update's 2 x 2 waves are the panel's");
+    __shared__ __attribute__((aligned(16))) GjPanelShared<NW, RPL> sh;
+    __shared__ __attribute__((aligned(16))) double s_inv[4 * 256];      // the four 16 x 16 triangular inverses, column-major
+    __shared__ int s_rowpos[64 * NW * RPL];
+    __shared__ int s_perm[GJ_NB];
+    const int chain = blockIdx.y;
+    double* __restrict__ A = Am.at(chain);
+    double* __restrict__ B = Bm.at(chain);
+    double* __restrict__ SA = SAm.at(chain);
+    double* __restrict__ X = Xm.at(chain);
+    const int* rowpos_old = rowpos_old_p + (long)chain * rowpos_stride;
+    int* rowpos_new = rowpos_new_p + (long)chain * rowpos_stride;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+#ifdef DQ_GJ_STAMPS
+    unsigned long long gentry, gstart, gprev;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gentry) :: "memory");
+#endif
+    const int nbw = min(GJ_NB, n - k0);
+
+    // ---- the panel's rows, then the operands of the update that depend on no pivot ----
+    unsigned live;
+    int oldpos[RPL], mypos[RPL], myperm;
+    double a[RPL][GJ_NB];
+    gj_panel_load<NW, RPL, true>(A, rowpos_old, n, k0, nbw, t, a, live, oldpos);
+
+    const int row_tiles = nA + nS + 1;
+    const int rt = blockIdx.x % row_tiles, ct = blockIdx.x / row_tiles;
+    const int r16 = lane & 15, kk = lane >> 4;
+    const int wr = wave & 1, wc = wave >> 1;
+    const bool colA = ct < nCA;
+    const int col = (colA ? k0 + nbw + 32 * ct : 32 * (ct - nCA)) + 16 * wc + r16;      // this lane's column (B operand / D layout)
+    const bool col_ok = col < n;
+    const long coff = (long)n * (col_ok ? col : n - 1);
+    const double* __restrict__ src12 = colA ? A : B;         // pivot rows are read from here
+    double* __restrict__ dstS = colA ? SA : X;               // retired rows of this column block
+    const bool writer = rt == nA + nS;
+    const bool rowS = rt >= nA;
+    const int row0 = (rowS ? 32 * (rt - nA) : 32 * rt) + 16 * wr;         // A rows: original index; S rows: pivot position
+    const int rowlim = rowS ? k0 : n;
+    const double* __restrict__ msrc = rowS ? SA : A;         // multipliers A[r, panel]
+    double* __restrict__ dst = rowS ? dstS : (colA ? A : B);
+    double mult[2][4];                                       // Mult[row0 + r16][k = 16h + kk + 4s]
+    double cold[4];                                          // C[row0 + kk + 4 reg][col]
+    {                                                        // the writer tile (rowlim = k0, possibly 0) loads too and uses nothing of it
+        const int mrow = max(min(row0 + r16, rowlim - 1), 0);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int k = 16 * h + kk + 4 * s;
+                const double v = msrc[mrow + (long)n * (k0 + (k < nbw ? k : 0))];
+                mult[h][s] = k < nbw ? v : 0.0;
+            }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) cold[reg] = dst[max(min(row0 + kk + 4 * reg, rowlim - 1), 0) + coff];
+    }
+
+#ifdef DQ_GJ_STAMPS
+    gj_panel_factor<NW, RPL>(sh, a, live, mypos, myperm, t, nbw, k0, gstart, gprev);
+#else
+    gj_panel_factor<NW, RPL>(sh, a, live, mypos, myperm, t, nbw, k0);
+#endif
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+        const int r = t + 64 * NW * q;
+        const int np = mypos[q] >= 0 ? mypos[q] : oldpos[q];
+        s_rowpos[r] = np;
+        if (blockIdx.x == 0 && r < n) rowpos_new[r] = np;
+    }
+    if (wave == 0 && lane < GJ_NB) s_perm[lane] = lane < nbw ? myperm : 0;
+    __syncthreads();
+#ifdef DQ_GJ_STAMPS
+    unsigned long long gmid, ginv, ggather;
+    GJ_STAMP_VM(gmid);
+#endif
+
+    // ---- the pivot rows of this wave's columns: the only loads behind the chain, in flight under the triangular inverses ----
+    double a12[2][4];                                        // A12[k = 16h + 4s + kk][col]
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = 16 * h + 4 * s + kk;
+            const double v = src12[s_perm[k < nbw ? k : 0] + coff];
+            a12[h][s] = (k < nbw && col_ok) ? v : 0.0;
+        }
+    bool st_ok[4];
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int r = row0 + kk + 4 * reg;
+        st_ok[reg] = !writer && col_ok && r < rowlim && (rowS || s_rowpos[max(min(r, rowlim - 1), 0)] < 0);
+    }
+    if (wave == 0) gj_panel_tri_inverses(sh.LU, s_inv, lane);
+    else if (wave == 1 && blockIdx.x == 0) gj_panel_logdet(sh.LU, logabsdet, accumulate, info, chain, lane, nbw, k0, sh.s_sing);
+#ifdef DQ_GJ_STAMPS
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ginv) :: "memory");
+#endif
+    __syncthreads();
+#ifdef DQ_GJ_STAMPS
+    GJ_STAMP_VM(ggather);
+#endif
+
+    // ---- triangular operands (A operand of the MFMA: row r16, k = 4 s + kk) ----
+    const double* LUs = &sh.LU[0][0];
+    double lai[4], lbi[4], uai[4], ubi[4], cl[4], cu[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int k = 4 * s + kk;
+        lai[s] = s_inv[0 * 256 + r16 + 16 * k]; lbi[s] = s_inv[1 * 256 + r16 + 16 * k];
+        uai[s] = s_inv[2 * 256 + r16 + 16 * k]; ubi[s] = s_inv[3 * 256 + r16 + 16 * k];
+        cl[s] = -LUs[(16 + r16) * 32 + k];               // -L11[16 + r16][k]
+        cu[s] = -LUs[r16 * 32 + 16 + k];                 // -U11[r16][16 + k]
+    }
+    // ---- T1 = L11^-1 A12, U12 = U11^-1 T1: gj_update_kernel's sequence ----
+    const d4 zero4 = {0.0, 0.0, 0.0, 0.0};
+    d4 t1[2], u[2];
+    t1[0] = zero4;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) t1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(lai[s], a12[0][s], t1[0], 0, 0, 0);
+    d4 w = {a12[1][0], a12[1][1], a12[1][2], a12[1][3]};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) w = __builtin_amdgcn_mfma_f64_16x16x4f64(cl[s], t1[0][s], w, 0, 0, 0);
+    t1[1] = zero4;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) t1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(lbi[s], w[s], t1[1], 0, 0, 0);
+    u[1] = zero4;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) u[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(ubi[s], t1[1][s], u[1], 0, 0, 0);
+    w = t1[0];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) w = __builtin_amdgcn_mfma_f64_16x16x4f64(cu[s], u[1][s], w, 0, 0, 0);
+    u[0] = zero4;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) u[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(uai[s], w[s], u[0], 0, 0, 0);
+    if (writer) {                                            // rows k0 + 16 wr + kk + 4 reg of SA / X receive U12
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int i = 16 * wr + kk + 4 * reg;
+            if (i < nbw && col_ok) dstS[k0 + i + coff] = u[wr][reg];
+        }
+    } else {
+        // ---- C -= Mult U12 ----
+        d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(mult[h][s], u[h][s], acc, 0, 0, 0);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg)
+            if (st_ok[reg]) dst[row0 + kk + 4 * reg + coff] = cold[reg] - acc[reg];
+    }
+#ifdef DQ_GJ_STAMPS
+    unsigned long long gend;
+    GJ_STAMP_VM(gend);
+    if (t == 0 && k0 == 0 && blockIdx.x == 0 && blockIdx.y == 0)
+        printf("   fused step: prologue %llu | chain %llu | deposit (+ printf) %llu | inverses (wave 0) %llu | gather wait %llu | update %llu\n", gstart - gentry, gprev - gstart,
+               gmid - gprev, ginv - gmid, ggather - ginv, gend - ggather);
+#endif
+}
+bool gj_fused_fits(int n) { return n > 64 && n <= 256; }
+// where the fused step measured faster than the two launches: with three or four waves of rows.  At n <= 128 the panel kernel
+// runs two waves and its barrier is cheaper than that of the step's four (n = 72, 100: 26.1 / 26.5 us per pair against 27.5 / 28.0 us per step).
+bool gj_fused_default(int n) { return n > 128 && n <= 256; }
+
 // X = A^-1 B (n <= 1024).  A and B are destroyed; SA: n*n scratch per chain; tinv: 2048 doubles per chain;
-// perm / rowpos: n ints per chain.  logabsdet (optional) receives (+)= log|det A|; *info |= DQ_STATUS_PIVOT on a zero / NaN pivot.
-int launch_gj_solve(Mat A, Mat B, Mat X, Mat SA, double* tinv, int* perm, long perm_stride, int* rowpos, long rowpos_stride,
-                    double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, hipStream_t s) {
+// perm / rowpos / rowpos_alt: n ints per chain.  logabsdet (optional) receives (+)= log|det A|; *info |= DQ_STATUS_PIVOT on a zero / NaN pivot.
+// fused: one gj_step_kernel per panel where an instance exists (gj_fused_fits); rowpos_alt is then the second half of rowpos.
+int launch_gj_solve(Mat A, Mat B, Mat X, Mat SA, double* tinv, int* perm, long perm_stride, int* rowpos, int* rowpos_alt, long rowpos_stride,
+                    double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, bool fused, hipStream_t s) {
     if (n > 1024) { set_error("gj_solve supports n <= 1024"); return -1; }
+    if (fused && rowpos_alt && gj_fused_fits(n)) {
+        int p = 0;
+        for (int k0 = 0; k0 < n; k0 += GJ_NB, ++p) {
+            const int nbw = n - k0 < GJ_NB ? n - k0 : GJ_NB;
+            const int nA = (n + 31) / 32, nS = k0 / 32;
+            const int nCA = (n - k0 - nbw + 31) / 32, nCB = (n + 31) / 32;
+            hipLaunchKernelGGL((gj_step_kernel<4, 1>), dim3((nA + nS + 1) * (nCA + nCB), n_chains), dim3(256), 0, s, A, B, SA, X, (const int*)((p & 1) ? rowpos_alt : rowpos),
+                               (p & 1) ? rowpos : rowpos_alt, rowpos_stride, logabsdet, accumulate_logdet, info, n, k0, nA, nS, nCA);
+        }
+        DQ_HIP(hipGetLastError());
+        return 0;
+    }
     for (int k0 = 0; k0 < n; k0 += GJ_NB) {
         const dim3 pg(1, n_chains);
 #define DQ_GJ_PANEL(NW, RPL) hipLaunchKernelGGL((gj_panel_mw_kernel<NW, RPL>), pg, dim3(RPL == 1 ? 64 * ((n + 63) / 64) : 64 * NW), 0, s, CMat(A), rowpos, rowpos_stride, perm, perm_stride, tinv, logabsdet, accumulate_logdet, info, n, k0)

@@ -1,5 +1,6 @@
 """Gauss-Jordan panel A/B: inv(I + F1 F2) through the stateless ABI at several sizes; prints a digest of the result bits and the error
-against numpy, so two builds / switches can be compared bit for bit.  usage: gj_probe.py [n ...]"""
+against numpy, so two builds / switches (DQMC_GJ_FUSED=0 / 1: two launches per panel / the fused step) can be compared bit for bit.
+usage: gj_probe.py [n ...]"""
 import hashlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

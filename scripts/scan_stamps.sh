@@ -1,6 +1,6 @@
 #!/bin/bash
 # diagnostic builds with s_memtime stamps (never used for timing results): libraries under scripts/stamp_build/, read by
-# scripts/sm_stamps.py (update kernels) and scripts/qr_stamps.py (column-owner QRCP)
+# scripts/sm_stamps.py (update kernels), scripts/qr_stamps.py (column-owner QRCP) and scripts/gj_stamps.py (Gauss-Jordan panel / fused step)
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p scripts/stamp_build
@@ -12,3 +12,5 @@ L="-L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib"
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o scripts/stamp_build/libdqmc_hip_scan.so $(ls dqmc_amd/csrc/*.o | grep -v "csrc/update.o") scripts/stamp_build/update.o $L
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o scripts/stamp_build/libdqmc_hip_sm.so $(ls dqmc_amd/csrc/*.o | grep -v "csrc/update_sm.o") scripts/stamp_build/update_sm.o $L
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o scripts/stamp_build/libdqmc_hip_qr.so $(ls dqmc_amd/csrc/*.o | grep -v "csrc/qr_colown.o") scripts/stamp_build/qr_colown.o $L
+/opt/rocm/bin/hipcc $F -DDQ_GJ_STAMPS -c dqmc_amd/csrc/lu_gj.hip -o scripts/stamp_build/lu_gj.o
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o scripts/stamp_build/libdqmc_hip_gjst.so $(ls dqmc_amd/csrc/*.o | grep -v "csrc/lu_gj.o") scripts/stamp_build/lu_gj.o $L
