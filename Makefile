@@ -14,6 +14,7 @@ $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/wave.h include/dqmc_hip.h
 
 $(CSRC)/qr_colown.o: $(CSRC)/qr_colown_regs.inc
 $(CSRC)/update.o: $(CSRC)/walk_bodies.inc
+$(CSRC)/gemm.o $(CSRC)/update.o: $(CSRC)/gemm_tile.h
 $(CSRC)/rng.o: $(CSRC)/philox.h
 $(CSRC)/walk_bodies.inc: scripts/gen_walk_bodies.py
 	python3 scripts/gen_walk_bodies.py

@@ -48,7 +48,7 @@ ABI_SYMBOLS = [
     "create", "create_batch", "n_chains", "destroy", "set_fields", "get_fields", "init", "get_G", "set_G", "get_logdet",
     "n_stack", "get_stack", "sweep_0_to_beta", "sweep_beta_to_0", "sync", "get_stats",
     "wrap_forward", "wrap_backward", "local_update_slice", "calculate_Bbar", "global_action", "set_checkerboard",
-    "update_kernel_time", "set_profiling", "slice_path", "debug_snapshot", "debug_gt_check",
+    "update_kernel_time", "set_profiling", "slice_path", "debug_snapshot", "bbar_rider_launches", "debug_gt_check",
     "measure_equal_time", "measure_accumulate", "measure_fetch",
     "sweep_unequal_time", "get_G_tau", "half_warp", "measure_unequal_time", "measure_unequal_fetch",
     "comm_unique_id", "comm_create_rccl", "comm_create_callbacks", "comm_destroy", "comm_rank", "comm_world_size",
@@ -130,6 +130,8 @@ class DqmcLib:
             g("half_warp").argtypes = [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int, c_double_p]
         if self.has_symbol("debug_snapshot"):
             g("debug_snapshot").argtypes = [C.c_void_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if self.has_symbol("bbar_rider_launches"):
+            g("bbar_rider_launches").argtypes = [C.c_void_p, c_int64_p]
         if self.has_symbol("debug_gt_check"):
             g("debug_gt_check").argtypes = [C.c_void_p, C.c_int, c_double_p, c_int64_p]
         if self.has_symbol("replica_exchange_round"):
@@ -552,6 +554,10 @@ class Engine:
         err = np.zeros(self.C); cnt = np.zeros(1, dtype=np.int64)
         self._c("debug_gt_check", int(bool(on)), _p(err), cnt.ctypes.data_as(c_int64_p))
         return err, int(cnt[0])
+
+    def bbar_rider_launches(self) -> int:
+        """dqmc_bbar_rider_launches: slice launches so far that carried a product of the B-bar chain in their flush workgroups."""
+        n = C.c_int64(0); self._c("bbar_rider_launches", C.byref(n)); return int(n.value)
 
     def slice_path(self) -> int:
         """dqmc_slice_path: 0 = scan / flush kernel pairs, 1 = persistent single-launch slice kernel, 2 = persistent, and at least one

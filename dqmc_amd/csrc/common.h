@@ -188,6 +188,13 @@ struct UpdateTables {            // per chain, 64 doubles: model constants the s
     double iev[4];
     double pad[32];
 };
+// A product C = diag(rs) A diag(ks) B for the flush workgroups of the persistent delayed-update kernel (slice_kernel, update.hip): a
+// GemmDesc cut down to its five pointers.  The kernel's arguments must stay small: 128 bytes more of them (a whole GemmDesc, even one
+// that no launch uses) cost every launch of that kernel 0.6 - 1.6 us.
+struct SliceRider {
+    const double* A = nullptr; const double* B = nullptr; double* C = nullptr; const double* rs = nullptr; const double* ks = nullptr;
+    __host__ __device__ GemmDesc gemm(int n) const { GemmDesc g; g.A = CMat(A, 0); g.B = CMat(B, 0); g.C = Mat{C, 0}; g.rs = CVec(rs, 0); g.ks = CVec(ks, 0); g.n = n; return g; }
+};
 struct UpdateDesc {
     Mat G;                        // current Green's function (n*n per chain)
     int8_t* fields; long f_stride;            // [chain][nt][n]
@@ -208,6 +215,10 @@ struct UpdateDesc {
     int* info = nullptr;                      // status block: |= DQ_STATUS_HANDOFF when a hand-off of a persistent slice kernel timed out
     int* acc_out; long acc_stride;            // per chain per slice accepted counts [chain][2*nt] (+ offset chosen by caller)
     int n, nt;
+    // optional rider of the persistent delayed-update kernel (slice_kernel, update.hip; every other kernel ignores it): an n x n product
+    // of a single-chain engine, computed by the flush workgroups before their first poll.  C null: none.
+    // It must not read the expv / invexpv row of the slice the launch walks (the walk rewrites that row in place).
+    SliceRider rider;
 };
 constexpr int UPDATE_KD = 32;    // delayed-update window (accepted flips per flush)
 

@@ -40,14 +40,15 @@ int init_device_kernels(int device) {
 // Kernel families of to_LDR, the solves and the local update, decided here and nowhere else (the per-size instance inside a family
 // is chosen next to its kernel) from n, the chain count, the CU reservation and the switches (README.md, "Environment switches").
 // ---------------------------------------------------------------------------
-struct Switches { bool qr_panel; int qr_panel_fused, gj_fused; bool qr_streaming, walk_submatrix, lu_classic, slice_multikernel; };
+struct Switches { bool qr_panel; int qr_panel_fused, gj_fused; bool qr_streaming, walk_submatrix, lu_classic, slice_multikernel, bbar_rider; };
 static const Switches& switches() {           // read once per process
     static const Switches sw = [] {
         const char* panel = getenv("DQMC_QR_PANEL");
         const char* fused = getenv("DQMC_QR_PANEL_FUSED");          // unset (-1): where it measured faster; 0: nowhere; 1: wherever an instance exists
         const char* gj = getenv("DQMC_GJ_FUSED");                   // the same three states for the Gauss-Jordan solve (lu_gj.hip)
+        const char* rider = getenv("DQMC_BBAR_RIDER");              // 0: the B-bar chain rides on the wraps again (wrap_*_piggy) instead of on the slice launches
         return Switches{!(panel && atoi(panel) == 0), fused ? (atoi(fused) != 0 ? 1 : 0) : -1, gj ? (atoi(gj) != 0 ? 1 : 0) : -1, getenv("DQMC_QR_STREAMING") != nullptr, getenv("DQMC_WALK_SUBMATRIX") != nullptr,
-                        getenv("DQMC_LU_CLASSIC") != nullptr, getenv("DQMC_SLICE_MULTIKERNEL") != nullptr};
+                        getenv("DQMC_LU_CLASSIC") != nullptr, getenv("DQMC_SLICE_MULTIKERNEL") != nullptr, !(rider && atoi(rider) == 0)};
     }();
     return sw;
 }
@@ -352,6 +353,7 @@ struct Engine {
     DevPtr<double> G, Gtmp, GT;                                  // [C][nn]; GT: transposed copy for the local-update walk
     DevPtr<double> pg_eye, pg_ones;                              // identity [nn] and ones [n]: operands of the first piggybacked B-bar factor of a block (single chain)
     DevPtr<double> bb0, bb1;                                     // Bbar ping-pong
+    long long rider_launches = 0;                                // slice launches that carried a B-bar product so far (dqmc_bbar_rider_launches)
     LdrStore stack;                                              // n_stack triples
     LdrStore spare;                                              // one spare triple (init)
     DevPtr<double> logdet;                                       // [C]
@@ -595,7 +597,23 @@ struct Engine {
     //   backward (wrap AFTER the update): the wrap of slice l ends with T diag(e^{V_l}) expK; beside it P <- P diag(e^{V_l}) expK = P B_l.
     // The first factor of a block multiplies the identity.  Same products, same kernel, same association in the forward sweep as Bbar();
     // in the backward sweep the chain is associated from the other end.
+    // With the persistent delayed-update kernel (bbar_rides()) a ridden product still cost ~3.4 us of the wrap it rode on (512 workgroups
+    // on 256 CUs), so the products move on to the next SLICE launch, whose flush workgroups are idle until the walk's first window
+    // (slice_rider, update.hip): the same operands, buffers and tile arithmetic, one launch later, and the wraps are single-chain again.
+    //   forward : the launch of slice l (loc >= 1) carries P <- diag(e^{V_{l-1}}) expK P -- slice l - 1 is final, slice l's row is not read;
+    //   backward: P <- P B_l is carried by the launch of slice l - 1; the product of a block's last slice in walking order (loc == 0)
+    //             stays on its wrap, because the stabilisation right behind it needs P.
+    // DQMC_BBAR_RIDER=0 keeps every product on the wraps.
     bool piggyback() const { return C == 1 && !cb && n <= 256 && pg_eye != nullptr; }
+    bool bbar_rides() const { return piggyback() && slice_path == SlicePath::PersistentWalk && switches().bbar_rider; }
+    SliceRider rider_forward(int l, const double* Pprev, double* Pnext) const {      // chain 1 of wrap_forward_piggy(l)
+        SliceRider r; r.A = expK.get(); r.B = Pprev; r.C = Pnext; r.rs = expv.get() + (long)(l - 1) * n;
+        return r;
+    }
+    SliceRider rider_backward(int l, const double* Pprev, double* Pnext) const {     // chain 1 of wrap_backward_piggy(l), without the scratch transpose
+        SliceRider r; r.A = Pprev; r.B = expK.get(); r.C = Pnext; r.ks = expv.get() + (long)l * n;
+        return r;
+    }
     int wrap_forward_piggy(int l, const double* Pprev, double* Pnext) {
         GemmDesc g; g.A = CMat(expK.get(), 0); g.B = CMat(G.get(), (long)(Pprev - G.get())); g.C = Mat{ctx.T(0).p, (long)(Pnext - ctx.T(0).p)};
         g.rs = CVec(pg_ones.get(), (long)((expv.get() + (long)(l - 1) * n) - pg_ones.get())); g.n = n;
@@ -631,7 +649,8 @@ struct Engine {
         d.panel_stride = (long)UPDATE_KD * n; d.state = state.get(); d.state_stride = 4; d.prep = prep.get(); d.prep_stride = 4L * n; d.slice_sync = is_persistent(slice_path) ? slice_sync.get() : nullptr; d.slice_epoch = slice_epoch; d.slice_absent_tile = slice_absent_tile; d.slice_absent_l = slice_absent_l; d.slice_late_tile = slice_late_tile; d.slice_late_us = slice_late_us; d.GT = Mat{GT.get(), nn}; d.gt_valid = gt_valid ? 1 : 0; d.info = ctx.info(); d.acc_out = acc.get(); d.acc_stride = nt; d.n = n; d.nt = nt;
         return d;
     }
-    int local_update(int l) {
+    // rider: a B-bar product for the flush workgroups of this launch (bbar_rides() only)
+    int local_update(int l, const SliceRider* rider = nullptr) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (profiling) {
             if (ev_used == ev_pairs.size()) { hipEvent_t a, b; DQ_HIP(hipEventCreate(&a)); DQ_HIP(hipEventCreate(&b)); ev_pairs.emplace_back(a, b); }
@@ -642,7 +661,10 @@ struct Engine {
             // every launch of a persistent slice kernel gets its own number: the hand-off words carry it, so none has to be re-armed
             if (++slice_epoch >= SLICE_EPOCH_LIMIT) { DQ_HIP(hipMemsetAsync(slice_sync.get(), 0, (size_t)C * SLICE_SYNC_BYTES, s)); slice_epoch = 1; }
         }
-        DQ_TRY(launch_update_slice(slice_path, udesc(), l, l, C, s));
+        UpdateDesc d = udesc();
+        if (rider) d.rider = *rider;
+        DQ_TRY(launch_update_slice(slice_path, d, l, l, C, s));
+        if (rider) ++rider_launches;
         if (profiling) DQ_HIP(hipEventRecord(e1, s));
         return 0;
     }
@@ -697,13 +719,16 @@ struct Engine {
     int sweep_fwd() {
         int n_err = 0;
         DQ_HIP(hipMemsetAsync(err.get(), 0, sizeof(double) * C * n_stack, s));       // max_abs_diff folds into zeroed slots
-        const bool pg = piggyback();
+        const bool pg = piggyback(), ride = bbar_rides();
         double* Pcur = bb0.get(); double* Pnxt = bb1.get();
         for (int l = 0; l < nt; ++l) {
             const int is = stack_idx(l), loc = local_l(l);
-            if (pg && loc >= 1) { DQ_TRY(wrap_forward_piggy(l, loc == 1 ? pg_eye.get() : Pcur, Pnxt)); std::swap(Pcur, Pnxt); } // P = B_{l-1} ... B_{l0}
-            else DQ_TRY(wrap_forward(l));
-            DQ_TRY(local_update(l));
+            if (pg && loc >= 1) {                                                             // P = B_{l-1} ... B_{l0}
+                const double* Pprev = loc == 1 ? pg_eye.get() : Pcur;
+                if (ride) { const SliceRider r = rider_forward(l, Pprev, Pnxt); DQ_TRY(wrap_forward(l)); DQ_TRY(local_update(l, &r)); }
+                else { DQ_TRY(wrap_forward_piggy(l, Pprev, Pnxt)); DQ_TRY(local_update(l)); }
+                std::swap(Pcur, Pnxt);
+            } else { DQ_TRY(wrap_forward(l)); DQ_TRY(local_update(l)); }
             if (loc == loc_l_end[is]) {
                 std::swap(G, Gtmp);                                                          // the wrapped G is kept for check_error, the stabilised one is written into the other buffer (no copy)
                 Mat bb;
@@ -727,13 +752,18 @@ struct Engine {
     int sweep_bwd() {
         int n_err = 0;
         DQ_HIP(hipMemsetAsync(err.get(), 0, sizeof(double) * C * n_stack, s));
-        const bool pg = piggyback();
+        const bool pg = piggyback(), ride = bbar_rides();
         double* Pcur = bb0.get(); double* Pnxt = bb1.get();
+        SliceRider pending; bool have_pending = false;                                        // P B_{l+1}, carried by the launch of slice l
         for (int l = nt - 1; l >= 0; --l) {
-            DQ_TRY(local_update(l));
+            DQ_TRY(local_update(l, have_pending ? &pending : nullptr));
+            if (have_pending) { std::swap(Pcur, Pnxt); have_pending = false; }
             const int is = stack_idx(l);
-            if (pg) { DQ_TRY(wrap_backward_piggy(l, local_l(l) == loc_l_end[is] ? pg_eye.get() : Pcur, Pnxt)); std::swap(Pcur, Pnxt); } // P = B_hi ... B_l
-            else DQ_TRY(wrap_backward(l));
+            if (pg) {                                                                         // P = B_hi ... B_l
+                const double* Pprev = local_l(l) == loc_l_end[is] ? pg_eye.get() : Pcur;
+                if (ride && local_l(l) != 0) { DQ_TRY(wrap_backward(l)); pending = rider_backward(l, Pprev, Pnxt); have_pending = true; }
+                else { DQ_TRY(wrap_backward_piggy(l, Pprev, Pnxt)); std::swap(Pcur, Pnxt); }
+            } else DQ_TRY(wrap_backward(l));
             if (local_l(l) == 0) {
                 std::swap(G, Gtmp);
                 Mat bb;
@@ -1277,6 +1307,11 @@ int dqmc_debug_snapshot(dqmc_engine* h, double* wrap_err, int* accepted, unsigne
     if (accepted) DQ_HIP(hipMemcpy(accepted, e.acc.get(), sizeof(int) * e.nt, hipMemcpyDeviceToHost));
     if (sync_words) DQ_HIP(hipMemcpy(sync_words, e.slice_sync.get(), sizeof(unsigned int) * 80, hipMemcpyDeviceToHost));
     if (slice_epoch) *slice_epoch = e.slice_epoch;
+    return 0;
+}
+int dqmc_bbar_rider_launches(dqmc_engine* h, int64_t* n_launches) {
+    ENGINE_CALL(h);
+    if (n_launches) *n_launches = e.rider_launches;
     return 0;
 }
 int dqmc_debug_gt_check(dqmc_engine* h, int on, double* max_err, int64_t* n_checks) {

@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <mutex>
 #include "wave.h"
+#include "gemm_tile.h"
 
 namespace dq {
 
@@ -718,6 +719,35 @@ __device__ __attribute__((noinline)) void solo_flush(double* G, double* GT, cons
     for (int st = wave; st < n_st; st += 4 * 4) flush_tiles_lds<4>(G, GT, UW, st, 4, n_st, tiles16, n, k, lane);
 }
 
+// ---- the rider: a B-bar product in the flush workgroups' idle time ----
+// A flush workgroup has nothing to do until the walk publishes its first window, at least 15 us after the launch (the census comment
+// above).  The product P <- B P (or P B) of the B-bar chain that the sweep needs next depends only on buffers earlier launches wrote
+// (expK, the previous P, the e^V row of a slice that is already final), so the flush workgroups compute it there: flush workgroup f
+// takes the 16x16 tiles f, f + F, ... of d.rider with the split-K GEMM's own tile body (gemm_tile.h: 256 threads = its 4 waves, the same
+// bits as a launch of that kernel).  Plain loads and stores: nothing of it is shared inside the launch, the kernel boundary orders it
+// against the launches that wrote its operands and the ones that read P.  No hand-off word, no extra workgroup.
+// Inlined, at ONE call site: the registers of the KQ = 64 instance (64 operand VGPRs) live only in the flush role's prologue and stay
+// inside the kernel's v0..v127 budget (scripts/check_walk_regs.py).  The generic kernel runs the K partition the GEMM launcher would
+// pick for n (launch_gemm_main, gemm.hip: kq = 16 .. 64 at n <= 256) on that one instance -- four instances inlined cost it 140 spilled
+// VGPRs.  As a real call (the way solo_flush is one) the body takes 248 VGPRs and saves callee-saved registers in 112 bytes of scratch,
+// which every wave of every launch would then be given; it measured no faster.
+constexpr size_t SLICE_RIDER_LDS_OFF = 16;                            // behind bcast[2]
+constexpr size_t SLICE_RIDER_LDS = SLICE_RIDER_LDS_OFF + sizeof(double) * 4 * 4 * 64;
+template <int NFIX>
+__device__ __forceinline__ void slice_rider(const SliceRider& rd, int n, int f, int F, unsigned char* smem) {
+    if (__builtin_expect(!rd.C, 1)) return;                           // workgroup-uniform (a kernel argument); the tile body is laid out behind the kernel's own code
+    const GemmDesc g = rd.gemm(n);
+    const int chain = 0;                                              // a single-chain engine's product: the pointers are the matrices
+    double (*part)[4][64] = reinterpret_cast<double (*)[4][64]>(smem + SLICE_RIDER_LDS_OFF);
+    const int T = (n + 15) / 16;
+    const int kq = NFIX ? gemm_splitk_kq(NFIX) : gemm_splitk_kq(n);   // k per wave: the launcher's own formula
+    for (int tile = f; tile < T * T; tile += F) {
+        const int i0 = (tile % T) * 16, j0 = (tile / T) * 16;
+        gemm_splitk_tile<false, 64>(g, chain, i0, j0, part, kq);
+        __syncthreads();                                              // the partial sums have been read: the area is free for the next tile
+    }
+}
+
 // NFIX / KFIX: matrix size and window depth as compile-time constants (0 = taken from the arguments).  The headline size N = 256, kd = 32
 // gets its own instance: the LDS layout, the strides of the pair store and the tile grid become literals, which frees the scalar
 // registers the generic instance spills to VGPR lanes in the walk's loops (53 spilled SGPRs, ~1.8 us per slice)
@@ -740,14 +770,18 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, S
     if (blockIdx.x > 0) {
         // ================= flush role: one 32x32 tile of G, one 16x16 sub-tile per wave =================
         const int tile = blockIdx.x - 1;
-        if (tile == d.slice_absent_tile && (d.slice_absent_l < 0 || d.slice_absent_l == l)) return;                      // debug: a workgroup that never becomes resident
-        if (tile == d.slice_late_tile) {                              // debug: a workgroup that becomes resident LATE (after the walk's census has given up)
+        // debug: a workgroup that never becomes resident -- it skips its flush duty only (no check-in, no polling): a real workgroup always
+        // runs in the end, and P needs its tiles of the rider
+        const bool absent = tile == d.slice_absent_tile && (d.slice_absent_l < 0 || d.slice_absent_l == l);
+        if (!absent && tile == d.slice_late_tile) {                              // debug: a workgroup that becomes resident LATE (after the walk's census has given up)
             const unsigned long long t0 = wall_clock64();             // 100 MHz
             while (wall_clock64() - t0 < 100ull * (unsigned long long)d.slice_late_us) __builtin_amdgcn_s_sleep(64);
         }
         const int a0 = (tile % tiles_per_dim) * 32 + (wave & 1) * 16;
         const int b0 = (tile / tiles_per_dim) * 32 + (wave >> 1) * 16;
-        if (t == 0) __hip_atomic_store(&sy->arrive[tile], slice_tag(epoch, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // census: resident
+        if (!absent && t == 0) __hip_atomic_store(&sy->arrive[tile], slice_tag(epoch, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // census: resident
+        slice_rider<NFIX>(d.rider, n, tile, F, smem);                  // the B-bar product that rides on this launch, in the time before the first window
+        if (absent) return;
         // one wave polls the window word (64 workgroups x 4 waves polling one L2 line slow the walk's own loads: guide, Pitfall 9),
         // the others wait at the barrier and take the word from LDS
         unsigned long long* bcast = reinterpret_cast<unsigned long long*>(smem);
@@ -978,7 +1012,7 @@ int launch_update_slice(SlicePath path, const UpdateDesc& d, int l, int acc_slot
     const int kd = pick_kd(n);
     const int threads = ((n + 63) / 64) * 64;
     const bool regs = threads <= 256;                               // walk v3 (register-resident pending pairs, needs GT)
-    const size_t lds = scan_lds_bytes(n, kd, regs);
+    size_t lds = scan_lds_bytes(n, kd, regs);
     const int tiles = (n + 31) / 32;
     if (!regs && path != SlicePath::Pairs && path != SlicePath::PersistentSubmatrix) { set_error("local update: the walk kernels of update.hip need n_sites <= 256"); return -1; }
     if (regs || path == SlicePath::PersistentSubmatrix) {          // the walk reads rows of G from GT
@@ -989,6 +1023,16 @@ int launch_update_slice(SlicePath path, const UpdateDesc& d, int l, int acc_slot
     case SlicePath::PersistentSubmatrix: return launch_update_slice_sm(d, l, acc_slot, n_chains, s);     // sub-matrix updates (update_sm.hip)
     case SlicePath::PersistentWalk:                                 // persistent single-launch kernel: every workgroup of a chain resident at once
         if (!d.slice_sync) { set_error("persistent slice kernel: hand-off words missing"); return -1; }
+        if (d.rider.C) {
+            if (n_chains != 1 || !d.rider.A || !d.rider.B) { set_error("persistent slice kernel: malformed rider product"); return -1; }
+            if (gemm_splitk_kq(n) > 64) { set_error("persistent slice kernel: the rider's split-K instance covers n <= 256"); return -1; }
+            // the walk rewrites the e^{+-V} rows of slice l in place: a scaling vector of the rider must lie outside them
+            const double* rows[2] = {d.expv + (long)l * n, d.invexpv + (long)l * n};
+            for (const double* v : {d.rider.rs, d.rider.ks})
+                for (const double* row : rows)
+                    if (v && row && v + n > row && v < row + n) { set_error("persistent slice kernel: the rider reads the e^V row of the slice this launch walks"); return -1; }
+            if (lds < SLICE_RIDER_LDS) lds = SLICE_RIDER_LDS;         // the flush workgroups' split-K area (tiny n only: the walk's pair store is larger otherwise)
+        }
         if (n == 256 && kd == UPDATE_KD)
             hipLaunchKernelGGL((slice_kernel<256, UPDATE_KD>), dim3(1 + tiles * tiles, n_chains), dim3(256), lds, s, d, reinterpret_cast<SliceSync*>(d.slice_sync), l, acc_slot, kd,
                                tiles, d.info);

@@ -407,6 +407,11 @@ int dqmc_slice_path(dqmc_engine* e);
  * (seq lo, seq hi, error, solo_count, 12 pad, arrive[0..63]); *slice_epoch: launches of that kernel so far.  Any pointer may be
  * NULL.  Synchronises the engine's stream.  No counterpart.                                                              */
 int dqmc_debug_snapshot(dqmc_engine* e, double* wrap_err, int* accepted, unsigned int* sync_words, unsigned int* slice_epoch);
+/* Diagnostic: *n_launches = launches of the persistent slice kernel that carried a product of the B-bar chain in their flush
+ * workgroups since the engine was created (single chain, dense kinetic factor, N <= 256, persistent delayed-update kernel; 0 with
+ * DQMC_BBAR_RIDER=0 and wherever the products ride on the wrap GEMMs instead).  Per sweep of whole blocks: n_stack (n_stab - 1).
+ * Does not synchronise.  No counterpart.                                                                                      */
+int dqmc_bbar_rider_launches(dqmc_engine* e, int64_t* n_launches);
 /* Diagnostic of the transposed copy of G the local-update walk reads.  A stabilisation of the backward sweep writes it from the
  * product that writes G; while `on` is 1, each of them is followed by a comparison with an explicit transpose of G.  The call
  * returns, of the checks since the previous call, max_err[n_chains] = max|GT - G^T| (NaN propagates) and *n_checks, clears both,
