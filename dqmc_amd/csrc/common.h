@@ -201,7 +201,7 @@ struct UpdateDesc {
     double* expv; double* invexpv; long v_stride;   // [chain][nt][n]
     const UpdateTables* tabs;                 // [chain]
     const int32_t* perm; const uint8_t* kprop; const double* u; long rs_stride;  // random stream [chain][nt][n]
-    double* Upanel; double* Wpanel; long panel_stride;   // [chain][KD][n]
+    double* Upanel; double* Wpanel; long panel_stride;   // [chain][KD][n]; the streaming persistent walk: rings [chain][SLICE_RING_ROWS][n]
     double* Cpanel = nullptr;                 // [chain][KD][KD]: the window's k x k matrix of the sub-matrix walk (update_sm.hip); null -> delayed-update walk
     int* state; long state_stride;            // per chain: [0]=pos, [1]=k (accepts in current window), [2]=accepted in slice
     double* prep; long prep_stride;           // per chain 4*n doubles: the slice's G-independent proposal data
@@ -228,7 +228,8 @@ constexpr int UPDATE_KD = 32;    // delayed-update window (accepted flips per fl
 // so a word left behind by an earlier launch can never match and nothing has to be re-armed when a launch ends (the round-2
 // kernels zeroed the words through an exit ticket: 66 stores and one atomic per workgroup on the tail of every launch).  The host
 // zeroes the block and restarts the epoch before it reaches 2^24 (Engine::local_update, engine.hip).
-//   seq       walk -> flush: high word = tag of the window just closed, low word = k | solo << 30 | final << 31
+//   seq       walk -> flush: high word = tag of the window just closed, low word = k | base << 8 | solo << 30 | final << 31
+//             (base: ring row of the window's pair 0 when the walk streams its pairs, slice_kernel; 0 otherwise)
 //   arrive[f] flush -> walk: tag of the last window flush workgroup f has absorbed; window 0 = "resident" (the census)
 struct SliceSync {
     unsigned long long seq; unsigned int error; unsigned int solo_count; unsigned int pad[12];    // 64 B
@@ -238,12 +239,18 @@ constexpr size_t SLICE_SYNC_BYTES = 2048;
 static_assert(sizeof(SliceSync) == SLICE_SYNC_BYTES, "SliceSync layout");
 constexpr unsigned SLICE_EPOCH_LIMIT = 1u << 24;
 constexpr unsigned SLICE_SOLO_BIT = 1u << 30, SLICE_FINAL_BIT = 1u << 31;
+// Streaming walk (slice_kernel, update.hip): Upanel / Wpanel are rings of 2 KD rows P[row][a].  Pair m of a window lives in row
+// (base + m) & (SLICE_RING_ROWS - 1); the walk holds at most KD pending pairs and drops a window's pairs only after every flush
+// workgroup has absorbed them, so a row is rewritten 2 KD pairs later, when the windows that read it are long confirmed.
+constexpr int SLICE_RING_ROWS = 2 * UPDATE_KD;
+constexpr unsigned SLICE_K_MASK = 0xffu, SLICE_BASE_SHIFT = 8, SLICE_BASE_MASK = SLICE_RING_ROWS - 1;
 __host__ __device__ inline unsigned slice_tag(unsigned epoch, unsigned window) { return (epoch << 8) | window; }
 // the local update of one time slice (chosen per engine by pick_slice_path, engine.hip): the persistent single-launch kernel with the
-// delayed-update walk (update.hip, n <= 256) or the sub-matrix walk (update_sm.hip), both need d.slice_sync and keep d.GT = G^T; the
+// delayed-update walk (update.hip, n <= 256; PersistentWalk streams every accepted pair to ring panels, PersistentWalkDump stores
+// them when a window closes) or the sub-matrix walk (update_sm.hip), all need d.slice_sync and keep d.GT = G^T; the
 // single-workgroup solo kernel (n <= 256); windows x (scan kernel, flush kernel), at n <= 256 keeping GT, optionally ending in one solo
 // launch that finishes the slice after four windows
-enum class SlicePath { PersistentWalk, PersistentSubmatrix, Solo, Pairs, PairsTailSolo };
+enum class SlicePath { PersistentWalk, PersistentWalkDump, PersistentSubmatrix, Solo, Pairs, PairsTailSolo };
 int launch_update_slice(SlicePath path, const UpdateDesc& d, int l, int acc_slot, int n_chains, hipStream_t s);
 // sub-matrix variant of the persistent single-launch slice kernel (update_sm.hip)
 int launch_update_slice_sm(const UpdateDesc& d, int l, int acc_slot, int n_chains, hipStream_t s);

@@ -40,15 +40,16 @@ int init_device_kernels(int device) {
 // Kernel families of to_LDR, the solves and the local update, decided here and nowhere else (the per-size instance inside a family
 // is chosen next to its kernel) from n, the chain count, the CU reservation and the switches (README.md, "Environment switches").
 // ---------------------------------------------------------------------------
-struct Switches { bool qr_panel; int qr_panel_fused, gj_fused; bool qr_streaming, walk_submatrix, lu_classic, slice_multikernel, bbar_rider; };
+struct Switches { bool qr_panel; int qr_panel_fused, gj_fused; bool qr_streaming, walk_submatrix, lu_classic, slice_multikernel, bbar_rider, slice_stream; };
 static const Switches& switches() {           // read once per process
     static const Switches sw = [] {
         const char* panel = getenv("DQMC_QR_PANEL");
         const char* fused = getenv("DQMC_QR_PANEL_FUSED");          // unset (-1): where it measured faster; 0: nowhere; 1: wherever an instance exists
         const char* gj = getenv("DQMC_GJ_FUSED");                   // the same three states for the Gauss-Jordan solve (lu_gj.hip)
         const char* rider = getenv("DQMC_BBAR_RIDER");              // 0: the B-bar chain rides on the wraps again (wrap_*_piggy) instead of on the slice launches
+        const char* stream = getenv("DQMC_SLICE_STREAM");           // 0: the persistent walk stores its pairs when a window closes (the dump) instead of one by one as they are accepted
         return Switches{!(panel && atoi(panel) == 0), fused ? (atoi(fused) != 0 ? 1 : 0) : -1, gj ? (atoi(gj) != 0 ? 1 : 0) : -1, getenv("DQMC_QR_STREAMING") != nullptr, getenv("DQMC_WALK_SUBMATRIX") != nullptr,
-                        getenv("DQMC_LU_CLASSIC") != nullptr, getenv("DQMC_SLICE_MULTIKERNEL") != nullptr, !(rider && atoi(rider) == 0)};
+                        getenv("DQMC_LU_CLASSIC") != nullptr, getenv("DQMC_SLICE_MULTIKERNEL") != nullptr, !(rider && atoi(rider) == 0), !(stream && atoi(stream) == 0)};
     }();
     return sw;
 }
@@ -90,13 +91,14 @@ static SlicePath pick_slice_path(int n, int chains, bool reserved) {
     if (sw.slice_multikernel) return SlicePath::Pairs;
     // sub-matrix updates at n <= 256 are opt-in: 211 us per cfg-3 slice against 138 us for the delayed-update walk -- the k x k algebra
     // is a dependent chain on one wave per SIMD (860 clk per two-proposal pass, 1780 clk per accepted flip), see DESIGN.md
-    if (reserved) return walk && !sw.walk_submatrix ? SlicePath::PersistentWalk : SlicePath::PersistentSubmatrix;
+    if (reserved) return walk && !sw.walk_submatrix ? (sw.slice_stream ? SlicePath::PersistentWalk : SlicePath::PersistentWalkDump) : SlicePath::PersistentSubmatrix;
     if (!walk) return SlicePath::Pairs;
     // measured (cfg 3, sweeps/s, solo vs pairs): 64 chains 166 / 214, 128 chains 251 / 275, 256 chains 324 / 307 -- a chain's own CU
     // flushes slower than the whole chip does, so the solo kernel pays once there are enough chains to occupy every CU
     return chains >= 224 ? SlicePath::Solo : SlicePath::PairsTailSolo;
 }
-static bool is_persistent(SlicePath p) { return p == SlicePath::PersistentWalk || p == SlicePath::PersistentSubmatrix; }
+static bool is_persistent_walk(SlicePath p) { return p == SlicePath::PersistentWalk || p == SlicePath::PersistentWalkDump; }
+static bool is_persistent(SlicePath p) { return is_persistent_walk(p) || p == SlicePath::PersistentSubmatrix; }
 
 // ---------------------------------------------------------------------------
 // Workspace + stable linear algebra on device (stablelinalg.cpp restated as
@@ -363,7 +365,8 @@ struct Engine {
     // half sweep the next sweep call without arrays draws
     bool rng_seeded = false; uint64_t rng_seed = 0; uint32_t rng_first_chain = 0, rng_counter = 0;
     hipEvent_t stage_free = nullptr;
-    DevPtr<double> Upanel, Wpanel;                               // [C][KD][n]
+    DevPtr<double> Upanel, Wpanel;                               // [C][panel_rows][n]
+    int panel_rows = UPDATE_KD;                                  // KD, or SLICE_RING_ROWS for the streaming persistent walk (create)
     DevPtr<double> Cpanel;                                       // [C][KD][KD]
     // The groups below are allocated on first use into a local group, which replaces the engine's only once all of it is allocated.
     // batched initialisation (init_batched): Bbar ping-pong [2][S][nn], tau [S][n] and the to_LDR of every block (S triples)
@@ -429,7 +432,8 @@ struct Engine {
         DQ_TRY(stack.alloc(n_stack, n, C, C <= 8)); DQ_TRY(spare.alloc(1, n, C));
         DQ_TRY(dev_alloc(logdet, C));
         DQ_TRY(dev_alloc(rs_perm, (size_t)C * nt * n)); DQ_TRY(dev_alloc(rs_k, (size_t)C * nt * n)); DQ_TRY(dev_alloc(rs_u, (size_t)C * nt * n));
-        DQ_TRY(dev_alloc(Upanel, (size_t)C * UPDATE_KD * n)); DQ_TRY(dev_alloc(Wpanel, (size_t)C * UPDATE_KD * n)); DQ_TRY(dev_alloc(Cpanel, (size_t)C * UPDATE_KD * UPDATE_KD));
+        panel_rows = slice_path == SlicePath::PersistentWalk ? SLICE_RING_ROWS : UPDATE_KD;     // the streaming walk's rings; every other path (and the one a failed persistent kernel is lowered to) uses the first KD rows
+        DQ_TRY(dev_alloc(Upanel, (size_t)C * panel_rows * n)); DQ_TRY(dev_alloc(Wpanel, (size_t)C * panel_rows * n)); DQ_TRY(dev_alloc(Cpanel, (size_t)C * UPDATE_KD * UPDATE_KD));
         DQ_TRY(dev_alloc(state, (size_t)C * 4)); DQ_TRY(dev_alloc(prep, (size_t)C * 4 * n)); DQ_TRY(dev_alloc(meas_now, (size_t)C * (3 + n))); DQ_TRY(dev_alloc(meas_sum, (size_t)C * (3 + n))); DQ_HIP(hipMemsetAsync(meas_sum.get(), 0, sizeof(double) * C * (3 + n), s)); DQ_TRY(dev_alloc(slice_sync, (size_t)C * SLICE_SYNC_BYTES)); DQ_HIP(hipMemsetAsync(slice_sync.get(), 0, (size_t)C * SLICE_SYNC_BYTES, s)); DQ_TRY(dev_alloc(acc, (size_t)C * nt)); DQ_TRY(dev_alloc(err, (size_t)C * n_stack));
         DQ_TRY(dev_alloc(dstats, C));
         void* stage = nullptr;
@@ -605,7 +609,7 @@ struct Engine {
     //             stays on its wrap, because the stabilisation right behind it needs P.
     // DQMC_BBAR_RIDER=0 keeps every product on the wraps.
     bool piggyback() const { return C == 1 && !cb && n <= 256 && pg_eye != nullptr; }
-    bool bbar_rides() const { return piggyback() && slice_path == SlicePath::PersistentWalk && switches().bbar_rider; }
+    bool bbar_rides() const { return piggyback() && is_persistent_walk(slice_path) && switches().bbar_rider; }
     SliceRider rider_forward(int l, const double* Pprev, double* Pnext) const {      // chain 1 of wrap_forward_piggy(l)
         SliceRider r; r.A = expK.get(); r.B = Pprev; r.C = Pnext; r.rs = expv.get() + (long)(l - 1) * n;
         return r;
@@ -646,7 +650,7 @@ struct Engine {
     UpdateDesc udesc() const {
         UpdateDesc d; d.G = mG(); d.fields = fields.get(); d.f_stride = (long)nt * n; d.expv = expv.get(); d.invexpv = invexpv.get(); d.v_stride = (long)nt * n;
         d.tabs = tabs.get(); d.perm = rs_perm.get(); d.kprop = rs_k.get(); d.u = rs_u.get(); d.rs_stride = (long)nt * n; d.Upanel = Upanel.get(); d.Wpanel = Wpanel.get(); d.Cpanel = Cpanel.get();
-        d.panel_stride = (long)UPDATE_KD * n; d.state = state.get(); d.state_stride = 4; d.prep = prep.get(); d.prep_stride = 4L * n; d.slice_sync = is_persistent(slice_path) ? slice_sync.get() : nullptr; d.slice_epoch = slice_epoch; d.slice_absent_tile = slice_absent_tile; d.slice_absent_l = slice_absent_l; d.slice_late_tile = slice_late_tile; d.slice_late_us = slice_late_us; d.GT = Mat{GT.get(), nn}; d.gt_valid = gt_valid ? 1 : 0; d.info = ctx.info(); d.acc_out = acc.get(); d.acc_stride = nt; d.n = n; d.nt = nt;
+        d.panel_stride = (long)panel_rows * n; d.state = state.get(); d.state_stride = 4; d.prep = prep.get(); d.prep_stride = 4L * n; d.slice_sync = is_persistent(slice_path) ? slice_sync.get() : nullptr; d.slice_epoch = slice_epoch; d.slice_absent_tile = slice_absent_tile; d.slice_absent_l = slice_absent_l; d.slice_late_tile = slice_late_tile; d.slice_late_us = slice_late_us; d.GT = Mat{GT.get(), nn}; d.gt_valid = gt_valid ? 1 : 0; d.info = ctx.info(); d.acc_out = acc.get(); d.acc_stride = nt; d.n = n; d.nt = nt;
         return d;
     }
     // rider: a B-bar product for the flush workgroups of this launch (bbar_rides() only)

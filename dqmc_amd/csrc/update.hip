@@ -203,8 +203,10 @@ __device__ __forceinline__ bool scan_group(const double (&pc)[SCAN_PF], const do
 //     2k FMAs run, nothing is masked, the code exists once;
 //   * the pivot's two prefetched G elements are picked lazily, on acceptance only, behind a counted s_waitcnt vmcnt(32) (the two
 //     younger groups' 32 loads may still be in flight); the row G[site, :] is read from the transposed copy GT (coalesced);
-//   * NO global store inside the walk: panel rows, fields and exp(V) entries are written when the window closes; barriers order
-//     LDS only; the diagonal is double-buffered in LDS (one barrier per accepted flip).
+//   * no global store the walk waits for: fields and exp(V) entries are written when the window closes, and so are the panel rows
+//     (the dump, walk_bodies.inc) except in the persistent kernel's streaming form, which stores each pair as it is formed without
+//     ever waiting for it inside a flip (SliceAsyncT below); barriers order LDS only; the diagonal is double-buffered in LDS (one
+//     barrier per accepted flip).
 #ifndef DQ_W6_KPUB
 #define DQ_W6_KPUB 24        // asynchronous windows: pairs per publish ...
 #define DQ_W6_XOVER 8        // ... and accepted flips the walk goes on for before it waits for their flush (SliceAsync)
@@ -284,19 +286,26 @@ __device__ __forceinline__ void slice_wait_arrivals(SliceSync* sy, unsigned epoc
 // reads no element of G meanwhile -- it lives on the columns already prefetched from G_old (the rest of this group and the next two)
 // and on room for 8 more pairs.  When either runs out, or the slice ends, it waits for the arrivals (by then mostly there), drops the
 // 24 applied pairs (registers and LDS rows 24 .. k-1 move down to 0 ..), and restarts the prefetch from the new G.
-struct NoAsync { static constexpr bool enabled = false; };
+//
+// STREAM: the walk stores every pair the moment it is formed (two sc1 8-byte stores per live lane, fire and forget) into ring panels of
+// SLICE_RING_ROWS rows, slot m of the current window in row (base + m) & 63, instead of writing a window's pairs out of its registers
+// when the window closes.  A pair is final when it is formed, so the transfer (98 KB per 24 pairs through one CU's 64 B/clk path) need
+// not wait for the window to close; a publish is then the drain of the last flip's stores, the barrier and the word, which carries base
+// (measured, DESIGN.md 5.6: a publish 4.9 k -> 1.3 k clk, the slice's last dump 4 k -> 0.6 k, and ~120 clk more per accepted flip).
+// Protocol and ordering are the dump form's: every storing wave drains, barrier, one lane stores the word.
+struct NoAsync { static constexpr bool enabled = false, stream = false; };
 __device__ __forceinline__ bool as_inflight(const NoAsync&) { return false; }
-struct SliceAsync {
-    static constexpr bool enabled = true;
+template <bool STREAM>
+struct SliceAsyncT {
+    static constexpr bool enabled = true, stream = STREAM;
     SliceSync* sy; unsigned epoch; int F; int* info; int* flag;
     unsigned win = 1;            // number of the next window to be published
     int published = 0;           // pairs handed off inside the walk (the caller's acceptance count)
     bool solo = false;
     bool inflight = false;       // a published window has not been waited for yet
     int g_limit = 0;             // last group whose columns were prefetched before the publish
+    unsigned base = 0;           // STREAM: ring row of pending pair 0 = pairs of this launch the flush workgroups have confirmed, modulo SLICE_RING_ROWS
 };
-
-__device__ __forceinline__ bool as_inflight(const SliceAsync& a) { return a.inflight; }
 
 template <bool COH, bool PANELS = true, class AS = NoAsync>
 __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, double& dg, int n, int kd, int j, bool live, const double* __restrict__ G,
@@ -320,6 +329,7 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
             if (live) for (int t = 0; t < k - DQ_W6_KPUB; ++t) sh.UW[t * n + j] = sh.UW[(DQ_W6_KPUB + t) * n + j];
             if (j < k - DQ_W6_KPUB) sh.acc_site[j] = sh.acc_site[DQ_W6_KPUB + j];
             k -= DQ_W6_KPUB; ++as.win; as.inflight = false;
+            as.base = (as.base + DQ_W6_KPUB) & SLICE_BASE_MASK;            // the confirmed window's ring rows are behind the walk now
             lds_barrier();
             DQ_ST(STAMP(tf2) prof.t_finwait += tf1 - tf0; prof.t_fin += tf2 - tf1;)
         }
@@ -376,7 +386,13 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
             const double pref = dl_p / r_p;                                      // source/model.cpp:132 (IEEE division) for the accepted proposal only, issued behind the LDS reads: its dozen dependent operations run under their latency
             // the pivot's G column / row elements from set gs: this group's 16 loads are done once at most the 32 younger ones are pending
             int ulo, uhi, wlo, whi;
-            asm volatile("s_waitcnt vmcnt(32)" ::: "memory");                   // (while a window is in flight nothing is outstanding at all: its publish drained)
+            // Streaming walk: the pair stores of earlier flips count in vmcnt too, and stores need not retire in order with loads.
+            // Let S be the stores issued after this group's loads and O the older operations still outstanding: O + 48 + S are
+            // outstanding at most (this group's 16 loads and the two younger groups' 32).  vmcnt(32) then guarantees at least
+            // 16 + S + O completions, of which at most S + O are not loads of these three groups, so at least 16 of those loads have
+            // completed; loads return in order among themselves, so they are this group's.  No order between stores and loads is
+            // assumed; outstanding stores only make the wait ask for a few of the younger loads as well.
+            asm volatile("s_waitcnt vmcnt(32)" ::: "memory");                   // (dump form: while a window is in flight nothing is outstanding at all, its publish drained)
             DQ_W6_PICK(gs * 8 + first);
             double uj = __hiloint2double(uhi, ulo), wj = __hiloint2double(whi, wlo);
             DQ_ST(STAMP(t1))
@@ -390,6 +406,15 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
                 dg += pu * wj;
                 if (live) { sh.UW[k * n + j] = make_double2(pu, wj); (par ? sh.diag : sh.diag2)[j] = dg; }     // slot k / the diagonal buffer no wave is reading
                 if (j == 0) sh.acc_site[k] = p;                                  // fields are written at window end
+                if constexpr (AS::stream) {
+                    // the pair leaves for ring row (base + k) & 63 now.  Inline asm, as the prefetch loads are: the compiler's waitcnt
+                    // pass does not see the stores, so nothing in the flip path waits for them (a publish and the window's end drain)
+                    const unsigned roff = (((as.base + (unsigned)k) & SLICE_BASE_MASK) * (unsigned)n + (unsigned)j) * 8u;
+                    // (s_nop: the panel bases are SGPRs the compiler may have just refilled from a spill lane with v_readlane_b32, and a VALU
+                    // write of an SGPR needs five wait states before a vector-memory instruction reads it as its address -- a hazard the
+                    // compiler covers for its own instructions only, not for the ones inside an asm statement; seen in the ISA)
+                    if (live) asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %3 sc1\n\tglobal_store_dwordx2 %0, %2, %4 sc1" :: "v"(roff), "v"(pu), "v"(wj), "s"(Up), "s"(Wp));
+                }
                 DQ_W6_SETPAIR(pu, wj);
             }
             DQ_ST(STAMP(t2))
@@ -400,7 +425,7 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
                 if (k == DQ_W6_KPUB && kd == UPDATE_KD && !as.inflight && !as.solo && pos < n) {
                     // ---- publish pairs 0 .. 23 and walk on ----
                     DQ_ST(unsigned long long tp0, tp1; STAMP(tp0))
-                    if (live) DQ_W6_DUMP_PUB;
+                    if constexpr (!AS::stream) { if (live) DQ_W6_DUMP_PUB; }    // (streaming: the 24 pairs are on their way already)
                     if (j < DQ_W6_KPUB) {
                         const int pp = sh.acc_site[j];
                         const int ii = sh.site[pp], new_f = sh.newf[pp];
@@ -428,7 +453,7 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
                         walk6_load_group<COH>(G, GT, sh, g + 2, (g + 2) % 3, n, j, live);
                     } else {
                         if (threadIdx.x == 0)
-                            __hip_atomic_store(&as.sy->seq, ((unsigned long long)slice_tag(as.epoch, as.win) << 32) | (unsigned)DQ_W6_KPUB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            __hip_atomic_store(&as.sy->seq, ((unsigned long long)slice_tag(as.epoch, as.win) << 32) | (as.base << SLICE_BASE_SHIFT) | (unsigned)DQ_W6_KPUB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         as.published += DQ_W6_KPUB; as.inflight = true; as.g_limit = g + 2;
                     }
                     DQ_ST(STAMP(tp1) prof.t_pub += tp1 - tp0; prof.n_pub++;)
@@ -454,7 +479,7 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
 #endif
     // (prefetch loads may still be in flight into their AGPR sets: the caller drains vmcnt before anything else can use them)
     // ---- window end: the flush's operands and the accepted field changes leave the workgroup (coalesced, from registers) ----
-    if (PANELS && live) DQ_W6_DUMP;
+    if constexpr (!AS::stream) { if (PANELS && live) DQ_W6_DUMP; }
     if (j < k) {
         const int p = sh.acc_site[j];
         const int i = sh.site[p], new_f = sh.newf[p];
@@ -572,16 +597,22 @@ __global__ __launch_bounds__(MAXT) DQ_WALK_REGS void scan_kernel(UpdateDesc d, i
 // stores are coalesced, instead of scattering the first chain's accumulators.
 // PAIRED: the panels are stored as P[m >> 1][a][m & 1] (what the register walk's window-end dump writes with 16-byte stores);
 // otherwise as P[m][a] (the LDS walk of n > 256, which stores rows as it goes).
-template <bool COH, bool WITH_GT, bool PAIRED>
+// RING (with !PAIRED): the panels are the streaming walk's rings, logical pair m in row (base + m) & (SLICE_RING_ROWS - 1).  The k-partition
+// m = 4 s + kk and the masking are unchanged, so the MFMA sums are the other layouts'.  The unconditional loads of all KD slots may then
+// read rows the walk is writing at that moment (the pairs 24 .. 31 of the window in flight): those slots are >= k, the select below
+// discards them, they are never multiplied.
+template <bool COH, bool WITH_GT, bool PAIRED, bool RING = false>
 __device__ __forceinline__ void flush_tile(double* __restrict__ G, double* __restrict__ GT, const double* __restrict__ Up, const double* __restrict__ Wp,
-                                           int a0, int b0, int n, int k, int kd, int lane) {
+                                           int a0, int b0, int n, int k, int kd, int lane, unsigned base = 0) {
+    static_assert(!(RING && PAIRED), "the rings are unpaired");
     const int r = lane & 15, kk = lane >> 4;
     const int a = min(a0 + r, n - 1), b = min(b0 + r, n - 1);          // clamped: loads stay unconditional
     const bool a_ok = a0 + r < n, b_ok = b0 + r < n;
     double uv[UPDATE_KD / 4], wv[UPDATE_KD / 4], gv[4], gt[4];
 #pragma unroll
     for (int s = 0; s < UPDATE_KD / 4; ++s) {
-        const int m = min(4 * s + kk, kd - 1);
+        const int ml = min(4 * s + kk, kd - 1);
+        const int m = RING ? (int)((base + (unsigned)ml) & SLICE_BASE_MASK) : ml;
         const int ib = PAIRED ? (m >> 1) * 2 * n + 2 * b + (m & 1) : m * n + b, ia = PAIRED ? (m >> 1) * 2 * n + 2 * a + (m & 1) : m * n + a;
         if (COH) { wv[s] = ld_coh(Wp + ib); uv[s] = ld_coh(Up + ia); }
         else { wv[s] = Wp[ib]; uv[s] = Up[ia]; }
@@ -751,7 +782,8 @@ __device__ __forceinline__ void slice_rider(const SliceRider& rd, int n, int f, 
 // NFIX / KFIX: matrix size and window depth as compile-time constants (0 = taken from the arguments).  The headline size N = 256, kd = 32
 // gets its own instance: the LDS layout, the strides of the pair store and the tile grid become literals, which frees the scalar
 // registers the generic instance spills to VGPR lanes in the walk's loops (53 spilled SGPRs, ~1.8 us per slice)
-template <int NFIX, int KFIX>
+// STREAM: the walk streams its pairs to ring panels (SliceAsyncT); false is the window-end dump (DQMC_SLICE_STREAM=0), an instance of its own
+template <int NFIX, int KFIX, bool STREAM>
 __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, SliceSync* sync_p, int l, int acc_slot, int kd_arg, int tiles_arg, int* info) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int chain = blockIdx.y;
@@ -811,9 +843,12 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, S
             if (word == ~0ULL) break;
             const unsigned lo = (unsigned)word;
             if (lo & SLICE_SOLO_BIT) break;                           // the walk applies the windows itself: G is not ours to touch
-            const int k = (int)(lo & 0x3fffffffu);
+            const int k = (int)(lo & SLICE_K_MASK);
             const bool final = (lo & SLICE_FINAL_BIT) != 0;
-            if (k > 0 && a0 < n && b0 < n) flush_tile<true, true, true>(G, GT, Up, Wp, a0, b0, n, k, kd, lane);
+            if (k > 0 && a0 < n && b0 < n) {
+                if constexpr (STREAM) flush_tile<true, true, false, true>(G, GT, Up, Wp, a0, b0, n, k, kd, lane, (lo >> SLICE_BASE_SHIFT) & SLICE_BASE_MASK);
+                else flush_tile<true, true, true>(G, GT, Up, Wp, a0, b0, n, k, kd, lane);
+            }
             if (final) break;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave drains before the arrival is signalled
             __syncthreads();
@@ -823,7 +858,7 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, S
     } else {
         // ================= walk role =================
         const int j = t;
-        const bool live = j < n;
+        const bool live = NFIX == 256 ? true : j < n;                 // (256 threads: at the literal size every lane owns a site, and the walk's exec-mask branches go)
         ScanShared sh;
         scan_shared_init(sh, smem, n, kd, true);
         const double* tab_g = reinterpret_cast<const double*>(d.tabs + chain);
@@ -847,9 +882,9 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, S
 #ifdef DQ_SCAN_STAMPS
         ScanProf prof; unsigned long long tk0, t_hand = 0; STAMP(tk0)
 #endif
-        SliceAsync as{sy, epoch, F, info, flag};
+        SliceAsyncT<STREAM> as{sy, epoch, F, info, flag};
         for (;; ++as.win) {
-            const int k = walk_window6<true, true, SliceAsync>(sh, pos, dg, n, kd, j, live, G, GT, d, slice_off, chain, fields_g, Up, Wp, as PROF_PASS);
+            const int k = walk_window6<true, true, SliceAsyncT<STREAM>>(sh, pos, dg, n, kd, j, live, G, GT, d, slice_off, chain, fields_g, Up, Wp, as PROF_PASS);
             total_acc += k + as.published; as.published = 0;
             const unsigned win = as.win;
             bool solo = as.solo;
@@ -857,6 +892,7 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, S
 #ifdef DQ_SCAN_STAMPS
             unsigned long long th0; STAMP(th0)
 #endif
+            // (streaming walk: the window's pairs were stored flip by flip, at ring rows base ..; what is left to drain is the last flip's)
             // census (first window): is every flush workgroup resident?  One coalesced load, issued in front of the drain of the panel
             // stores so that its round trip hides behind theirs (the workgroups checked in while the first window was walked)
             unsigned census = slice_tag(epoch, 0);
@@ -865,7 +901,7 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, S
             __syncthreads();
             if (win == 1) { solo = slice_census_missing(sy, epoch, F, census, flag); as.solo = solo; }
             if (t == 0) {
-                __hip_atomic_store(&sy->seq, ((unsigned long long)slice_tag(epoch, win) << 32) | (final ? SLICE_FINAL_BIT : 0u) | (solo ? SLICE_SOLO_BIT : 0u) | (unsigned)k,
+                __hip_atomic_store(&sy->seq, ((unsigned long long)slice_tag(epoch, win) << 32) | (final ? SLICE_FINAL_BIT : 0u) | (solo ? SLICE_SOLO_BIT : 0u) | (as.base << SLICE_BASE_SHIFT) | (unsigned)k,
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (solo && win == 1) __hip_atomic_fetch_add(&sy->solo_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -878,10 +914,12 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, S
                 __syncthreads();
                 if (live) sh.diag[j] = dg;
                 __syncthreads();
+                as.base = (as.base + (unsigned)k) & SLICE_BASE_MASK;  // (nobody reads the rings of a solo launch; the stores go on)
                 continue;
             }
             if (final) break;
             slice_wait_arrivals(sy, epoch, win, F, info);                // until every tile has absorbed this window
+            as.base = (as.base + (unsigned)k) & SLICE_BASE_MASK;
             // G changed: the prefetch restarts from memory.  The diagonal does not: the lane's running value dg (advanced by pu * wj at
             // every accepted flip) IS G_jj after the flush up to the summation order, so the next window starts from it instead of
             // paying an L2 round trip in front of the prefetch (it is re-read from G at the start of every slice)
@@ -1000,8 +1038,10 @@ void slice_release(int device, int n, int n_chains) {
 int update_init_device() {
     DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<256, UPDATE_KD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<0, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<256, UPDATE_KD, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<0, 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<256, UPDATE_KD, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_solo_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return 0;
 }
@@ -1021,7 +1061,9 @@ int launch_update_slice(SlicePath path, const UpdateDesc& d, int l, int acc_slot
     }
     switch (path) {
     case SlicePath::PersistentSubmatrix: return launch_update_slice_sm(d, l, acc_slot, n_chains, s);     // sub-matrix updates (update_sm.hip)
-    case SlicePath::PersistentWalk:                                 // persistent single-launch kernel: every workgroup of a chain resident at once
+    case SlicePath::PersistentWalk: case SlicePath::PersistentWalkDump: {   // persistent single-launch kernel: every workgroup of a chain resident at once
+        const bool stream = path == SlicePath::PersistentWalk;
+        if (stream && d.panel_stride < (long)SLICE_RING_ROWS * n) { set_error("persistent slice kernel: the panels are no rings"); return -1; }
         if (!d.slice_sync) { set_error("persistent slice kernel: hand-off words missing"); return -1; }
         if (d.rider.C) {
             if (n_chains != 1 || !d.rider.A || !d.rider.B) { set_error("persistent slice kernel: malformed rider product"); return -1; }
@@ -1033,14 +1075,12 @@ int launch_update_slice(SlicePath path, const UpdateDesc& d, int l, int acc_slot
                     if (v && row && v + n > row && v < row + n) { set_error("persistent slice kernel: the rider reads the e^V row of the slice this launch walks"); return -1; }
             if (lds < SLICE_RIDER_LDS) lds = SLICE_RIDER_LDS;         // the flush workgroups' split-K area (tiny n only: the walk's pair store is larger otherwise)
         }
-        if (n == 256 && kd == UPDATE_KD)
-            hipLaunchKernelGGL((slice_kernel<256, UPDATE_KD>), dim3(1 + tiles * tiles, n_chains), dim3(256), lds, s, d, reinterpret_cast<SliceSync*>(d.slice_sync), l, acc_slot, kd,
-                               tiles, d.info);
-        else
-            hipLaunchKernelGGL((slice_kernel<0, 0>), dim3(1 + tiles * tiles, n_chains), dim3(256), lds, s, d, reinterpret_cast<SliceSync*>(d.slice_sync), l, acc_slot, kd,
-                               tiles, d.info);
+        auto kern = n == 256 && kd == UPDATE_KD ? (stream ? slice_kernel<256, UPDATE_KD, true> : slice_kernel<256, UPDATE_KD, false>)
+                                                : (stream ? slice_kernel<0, 0, true> : slice_kernel<0, 0, false>);
+        hipLaunchKernelGGL(kern, dim3(1 + tiles * tiles, n_chains), dim3(256), lds, s, d, reinterpret_cast<SliceSync*>(d.slice_sync), l, acc_slot, kd, tiles, d.info);
         DQ_HIP(hipGetLastError());
         return 0;
+    }
     case SlicePath::Solo:
         hipLaunchKernelGGL(slice_solo_kernel, dim3(1, n_chains), dim3(256), lds, s, d, l, acc_slot, kd, 0);
         DQ_HIP(hipGetLastError());
