@@ -136,6 +136,7 @@ struct QrWork {
     double* pw = nullptr; long pw_stride = 0;                   // panel-pivoted QR (qr_panel.hip): sketches, Q accumulator, ticket counter (zero between calls); >= qr_panel_work_doubles(n, pw_two_launch) per chain
     bool pw_two_launch = false;                                 // ... with room for the reflector panels and T factors: the two-launch form (panel kernel + update kernel) is used at every n
     int* pivpos = nullptr; long pivpos_stride = 0;              // panel-pivoted QR: pivot position of every column (-1 = live), n per chain
+    bool pw_compact = true;                                     // panel-pivoted QR, 128 < n <= 256: panels with <= 128 live columns select on a compacted sketch in one wave (same bits; false: DQMC_PANEL_COMPACT=0)
 };
 bool qr_panel_fused_fits(int n);             // the one-launch-per-panel form has an instance for this n
 bool qr_panel_fused_default(int n);          // ... and is what to_LDR uses at this n unless DQMC_QR_PANEL_FUSED says otherwise
@@ -172,10 +173,11 @@ int launch_tri_solve(CMat R, const int* perm, long perm_stride, Mat X, CVec dg, 
 // logabsdet (optional): (+)= log|det A|.  *info |= DQ_STATUS_PIVOT on a zero / NaN pivot.
 // fused: one launch per panel (gj_step_kernel: every update workgroup factors the panel) where gj_fused_fits(n); rowpos and rowpos_alt
 // then alternate with the panel's parity.  Both forms give the same bits.
+// compact: the <4, 1> instances (n <= 256) run a panel with <= 128 live rows on one wave, the live rows in rank order (same pivots, same bits).
 bool gj_fused_fits(int n);                   // the one-launch-per-panel form has an instance for this n
 bool gj_fused_default(int n);                // ... and is what the solves use at this n unless DQMC_GJ_FUSED says otherwise
 int launch_gj_solve(Mat A, Mat B, Mat X, Mat SA, double* tinv, int* perm, long perm_stride, int* rowpos, int* rowpos_alt, long rowpos_stride,
-                    double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, bool fused, hipStream_t s);
+                    double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, bool fused, bool compact, hipStream_t s);
 
 // ---- update.hip ---------------------------------------------------------------
 struct UpdateTables {            // per chain, 64 doubles: model constants the slice kernel needs

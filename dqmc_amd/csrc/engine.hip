@@ -40,7 +40,7 @@ int init_device_kernels(int device) {
 // Kernel families of to_LDR, the solves and the local update, decided here and nowhere else (the per-size instance inside a family
 // is chosen next to its kernel) from n, the chain count, the CU reservation and the switches (README.md, "Environment switches").
 // ---------------------------------------------------------------------------
-struct Switches { bool qr_panel; int qr_panel_fused, gj_fused; bool qr_streaming, walk_submatrix, lu_classic, slice_multikernel, bbar_rider, slice_stream; };
+struct Switches { bool qr_panel; int qr_panel_fused, gj_fused; bool qr_streaming, walk_submatrix, lu_classic, slice_multikernel, bbar_rider, slice_stream, panel_compact; };
 static const Switches& switches() {           // read once per process
     static const Switches sw = [] {
         const char* panel = getenv("DQMC_QR_PANEL");
@@ -48,8 +48,9 @@ static const Switches& switches() {           // read once per process
         const char* gj = getenv("DQMC_GJ_FUSED");                   // the same three states for the Gauss-Jordan solve (lu_gj.hip)
         const char* rider = getenv("DQMC_BBAR_RIDER");              // 0: the B-bar chain rides on the wraps again (wrap_*_piggy) instead of on the slice launches
         const char* stream = getenv("DQMC_SLICE_STREAM");           // 0: the persistent walk stores its pairs when a window closes (the dump) instead of one by one as they are accepted
+        const char* compact = getenv("DQMC_PANEL_COMPACT");         // 0: the late panels of to_LDR and of the Gauss-Jordan solve (n <= 256) keep every column / row on its original lane, four waves to the last panel
         return Switches{!(panel && atoi(panel) == 0), fused ? (atoi(fused) != 0 ? 1 : 0) : -1, gj ? (atoi(gj) != 0 ? 1 : 0) : -1, getenv("DQMC_QR_STREAMING") != nullptr, getenv("DQMC_WALK_SUBMATRIX") != nullptr,
-                        getenv("DQMC_LU_CLASSIC") != nullptr, getenv("DQMC_SLICE_MULTIKERNEL") != nullptr, !(rider && atoi(rider) == 0), !(stream && atoi(stream) == 0)};
+                        getenv("DQMC_LU_CLASSIC") != nullptr, getenv("DQMC_SLICE_MULTIKERNEL") != nullptr, !(rider && atoi(rider) == 0), !(stream && atoi(stream) == 0), !(compact && atoi(compact) == 0)};
     }();
     return sw;
 }
@@ -204,6 +205,7 @@ struct Ctx {
         QrWork w{V(4).p, (long)n, keep ? out.jpvt : jpvt(), (long)n};
         w.sync = qsync.get(); w.sync_stride = qrcp_coop_sync_granules(n); w.abort_words = qabort.get(); w.info = info();
         w.pw = qpw.get(); w.pw_stride = qr_panel_work_doubles(n, qpw_two_launch); w.pw_two_launch = qpw_two_launch; w.pivpos = qpivpos.get(); w.pivpos_stride = n;
+        w.pw_compact = switches().panel_compact;
         if (out.tri) *out.tri = keep;
         out.touch();
         return launch_to_ldr(plan.qr, A, out.L, out.d, out.R, w, n, C, stream);
@@ -257,7 +259,7 @@ struct Ctx {
     // Returns the matrix holding Y in *Y.  M and RHS are destroyed.  (uses T5 as scratch)
     int solve(Mat M, Mat RHS, Mat out, double* logdet_acc, Mat* Y) {
         if (plan.solve == KernelPlan::Solve::GaussJordan) {
-            DQ_TRY(launch_gj_solve(M, RHS, out, T(5), tinv.get(), lperm(), n, rowpos(), rowpos_alt(), n, logdet_acc, 1, info(), n, C, gj_fused, stream));
+            DQ_TRY(launch_gj_solve(M, RHS, out, T(5), tinv.get(), lperm(), n, rowpos(), rowpos_alt(), n, logdet_acc, 1, info(), n, C, gj_fused, switches().panel_compact, stream));
             *Y = out; return 0;
         }
         DQ_TRY(launch_lu_blocked(M, lperm(), n, rowpos(), n, logdet_acc, 1, info(), n, C, stream));

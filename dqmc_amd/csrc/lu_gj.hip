@@ -32,6 +32,7 @@
 #include "common.h"
 #include "wave.h"
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 
 namespace dq {
@@ -227,6 +228,9 @@ __device__ __forceinline__ void gj_panel_tri_inverses(double (&LU)[GJ_NB][GJ_NB]
 }
 
 #ifdef DQ_GJ_STAMPS
+#ifndef DQ_GJ_STAMP_K0
+#define DQ_GJ_STAMP_K0 0         // the panel whose clocks the stamp build prints (-DDQ_GJ_STAMP_K0=192: a compacted one at n = 256)
+#endif
 // diagnostic build only (scripts/gj_stamps.py): where a step's time goes; s_memtime counts 100 MHz ticks
 #define GST(i) { unsigned long long t_; asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); gst[i] += t_ - gprev; gprev = t_; }
 #define GST_ARGS , unsigned long long (&gst)[8], unsigned long long& gprev
@@ -242,7 +246,10 @@ __device__ __forceinline__ void gj_panel_tri_inverses(double (&LU)[GJ_NB][GJ_NB]
 // and its candidate lane publishes {key, lane} and the row's live part (columns >= J) into the wave's LDS slot BEFORE the global
 // winner is known; after the barrier every wave reads the W keys, picks the winner (largest |a|, lowest wave on ties) and reads the
 // pivot row from the winner's slot.  Slots are double-buffered on the parity of J (a wave can be at most one step ahead).
-template <int J, int NW, int RPL>
+// VAL (the <4, 1> instance): the search inside a wave compares |a| without its low 9 bits as well, so that both levels apply one rule -- the
+// lowest row among those with the largest truncated |a| -- and the pivot is a function of the values alone, not of which rows share a wave
+// (without it two candidates of ONE wave that agree in their leading 43 mantissa bits are told apart, two of different waves are not).
+template <int J, int NW, int RPL, bool VAL>
 __device__ __forceinline__ void gj_step_mw(double (&a)[RPL][GJ_NB], unsigned& live, int (&mypos)[RPL], int& myperm, bool& singular, int lane, int wave, int k0,
                                            double (*slot_row)[NW][GJ_NB + 2], unsigned long long (*slot_key)[(NW + 1) & ~1] GST_ARGS) {
     constexpr int PAR = J & 1;
@@ -253,7 +260,8 @@ __device__ __forceinline__ void gj_step_mw(double (&a)[RPL][GJ_NB], unsigned& li
     // dynamically indexed array lives in scratch)
     double aj = a[0][J]; int bs = 0;
     if (RPL > 1) asm volatile("" : "+v"(aj));
-    unsigned long long key = (live & 1u) ? ((unsigned long long)__double_as_longlong(fabs(aj)) | 1ULL) : 0ULL;
+    unsigned long long key = (live & 1u) ? (VAL ? ((unsigned long long)__double_as_longlong(fabs(aj)) & ~0x1FFULL) | 0x100ULL : ((unsigned long long)__double_as_longlong(fabs(aj)) | 1ULL)) : 0ULL;
+    static_assert(!VAL || RPL == 1, "the truncated in-wave search is written for one row per lane");
 #pragma unroll
     for (int q = 1; q < RPL; ++q) {
         double v = a[q][J];
@@ -325,19 +333,112 @@ __device__ __forceinline__ void gj_step_mw(double (&a)[RPL][GJ_NB], unsigned& li
     }
     GST(6)
 }
-template <int J, int NW, int RPL>
+template <int J, int NW, int RPL, bool VAL>
 struct GjStepsMW {
     static __device__ __forceinline__ void run(double (&a)[RPL][GJ_NB], unsigned& live, int (&mypos)[RPL], int& myperm, bool& singular, int lane, int wave, int nbw, int k0,
                                                double (*slot_row)[NW][GJ_NB + 2], unsigned long long (*slot_key)[(NW + 1) & ~1] GST_ARGS) {
-        if (J < nbw) gj_step_mw<J, NW, RPL>(a, live, mypos, myperm, singular, lane, wave, k0, slot_row, slot_key GST_PASS);      // workgroup-uniform
-        GjStepsMW<J + 1, NW, RPL>::run(a, live, mypos, myperm, singular, lane, wave, nbw, k0, slot_row, slot_key GST_PASS);
+        if (J < nbw) gj_step_mw<J, NW, RPL, VAL>(a, live, mypos, myperm, singular, lane, wave, k0, slot_row, slot_key GST_PASS);      // workgroup-uniform
+        GjStepsMW<J + 1, NW, RPL, VAL>::run(a, live, mypos, myperm, singular, lane, wave, nbw, k0, slot_row, slot_key GST_PASS);
     }
 };
-template <int NW, int RPL>
-struct GjStepsMW<GJ_NB, NW, RPL> {
+template <int NW, int RPL, bool VAL>
+struct GjStepsMW<GJ_NB, NW, RPL, VAL> {
     static __device__ __forceinline__ void run(double (&)[RPL][GJ_NB], unsigned&, int (&)[RPL], int&, bool&, int, int, int, int, double (*)[NW][GJ_NB + 2],
                                                unsigned long long (*)[(NW + 1) & ~1] GST_ARGS) {}
 };
+// ---- compacted panel: the live rows in ONE wave -------------------------------------------------------------------------------
+// A late panel of the <4, 1> instance (n - k0 <= GJ_CMAX live rows) moves its live rows into rank order (= row order) through LDS and
+// wave 0 eliminates alone, C = 1 or 2 rows per lane (ranks C lane + q, so "lowest lane, lowest slot" is "lowest row"): the single-wave
+// step of gj_panel_kernel -- wave maxima, ballot, the pivot row by v_readlane into scalar operands, no LDS, no barrier -- with the pivot
+// rule and the arithmetic of gj_step_mw<.., VAL = true>: truncated keys, the reciprocal by v_rcp_f64 + two Newton steps of the pivot
+// element, l = a r, a <- fma(-l, p, a), dead rows with l = 0.  Same pivots, same bits.  A lane carries the ORIGINAL row of each slot.
+constexpr int GJ_CMAX = 128;
+struct GjCompactShared {
+    double rows[GJ_NB][GJ_CMAX];                         // [column][rank]: a wave's stores and loads run along the ranks
+    int orow[GJ_CMAX];                                   // rank -> original row
+    int pos[256];                                        // original row -> the pivot position it took in this panel, or -1
+};
+template <int J, int C>
+__device__ __forceinline__ void gj_step_cw(double (&a)[C][GJ_NB], unsigned& live, const int (&orow)[C], int (&pos)[C], int& myperm, bool& singular, int lane, int k0) {
+    unsigned long long key = 0ULL; int bq = 0;
+#pragma unroll
+    for (int q = 0; q < C; ++q) {
+        const unsigned long long kq = ((live >> q) & 1u) ? ((unsigned long long)__double_as_longlong(fabs(a[q][J])) & ~0x1FFULL) | 0x100ULL : 0ULL;
+        if (kq > key) { key = kq; bq = q; }               // strict: the lower slot (= the lower row) of the lane wins a tie
+    }
+    const unsigned hi = (unsigned)(key >> 32), lo = (unsigned)key;
+    const unsigned m1 = wave_max_u32(hi);
+    const unsigned m2 = wave_max_u32(hi == m1 ? lo : 0u);
+    const unsigned long long winners = __ballot(hi == m1 && lo == m2 && key != 0ULL);
+    const int pl = winners ? (int)__builtin_ctzll(winners) : 0;
+    const int pq = C > 1 ? __builtin_amdgcn_readlane(bq, pl) : 0;
+    double prow[GJ_NB - J]; int prw = 0;
+#pragma unroll
+    for (int q = 0; q < C; ++q) {
+        if (q == pq) {                                    // wave-uniform
+#pragma unroll
+            for (int c = J; c < GJ_NB; ++c) prow[c - J] = readlane_f64(a[q][c], pl);
+            prw = __builtin_amdgcn_readlane(orow[q], pl);
+        }
+    }
+    if (lane == J) myperm = prw;
+    const double piv = prow[0];
+    singular = singular || !(fabs(piv) > 0.0);
+    double r = __builtin_amdgcn_rcp(piv);
+    r = fma(fma(-piv, r, 1.0), r, r);
+    r = fma(fma(-piv, r, 1.0), r, r);
+#pragma unroll
+    for (int q = 0; q < C; ++q) {
+        if (lane == pl && pq == q) { live &= ~(1u << q); pos[q] = k0 + J; }
+        const bool lv = (live >> q) & 1u;
+        const double l = lv ? a[q][J] * r : 0.0;
+        a[q][J] = lv ? l : a[q][J];
+#pragma unroll
+        for (int c = J + 1; c < GJ_NB; ++c) a[q][c] = fma(-l, prow[c - J], a[q][c]);
+    }
+}
+template <int J, int C>
+struct GjStepsCW {
+    static __device__ __forceinline__ void run(double (&a)[C][GJ_NB], unsigned& live, const int (&orow)[C], int (&pos)[C], int& myperm, bool& singular, int lane, int nbw, int k0) {
+        if (J < nbw) gj_step_cw<J, C>(a, live, orow, pos, myperm, singular, lane, k0);      // wave-uniform
+        GjStepsCW<J + 1, C>::run(a, live, orow, pos, myperm, singular, lane, nbw, k0);
+    }
+};
+template <int C>
+struct GjStepsCW<GJ_NB, C> {
+    static __device__ __forceinline__ void run(double (&)[C][GJ_NB], unsigned&, const int (&)[C], int (&)[C], int&, bool&, int, int, int) {}
+};
+// wave 0, after the barrier behind the compaction: the nl live rows out of cs, the steps, then the pivot rows into LU (the identity fill
+// is behind the same barrier), their positions into cs.pos[original row] and the singular flag
+template <int C>
+__device__ __forceinline__ void gj_chain_cw(GjCompactShared& cs, double (&LU)[GJ_NB][GJ_NB], int& s_sing, int& myperm, int nl, int lane, int nbw, int k0) {
+    double a[C][GJ_NB]; int orow[C], pos[C];
+    unsigned live = 0u;
+#pragma unroll
+    for (int q = 0; q < C; ++q) {
+        const int slot = C * lane + q;
+        const bool ok = slot < nl;
+        const int sc = ok ? slot : 0;
+#pragma unroll
+        for (int c = 0; c < GJ_NB; ++c) { const double v = cs.rows[c][sc]; a[q][c] = ok ? v : 0.0; }
+        orow[q] = ok ? cs.orow[sc] : 0;
+        pos[q] = -1;
+        live |= ok ? (1u << q) : 0u;
+    }
+    bool singular = false;
+    GjStepsCW<0, C>::run(a, live, orow, pos, myperm, singular, lane, nbw, k0);
+#pragma unroll
+    for (int q = 0; q < C; ++q) {
+        if (pos[q] >= 0) {
+            cs.pos[orow[q]] = pos[q];
+            double* dst = &LU[pos[q] - k0][0];
+#pragma unroll
+            for (int c = 0; c < GJ_NB; c += 2) *reinterpret_cast<double2*>(dst + c) = make_double2(a[q][c], a[q][c + 1]);
+        }
+    }
+    if (singular && lane == 0) s_sing = 1;
+}
+
 // NW waves (the most the workgroup may have), RPL matrix rows per lane: row t + 64 NW q is slot q of thread t.  One wave per SIMD up to n = 768
 // (<4, 1> n <= 256, <4, 2> <= 512, <3, 3> <= 576, <4, 3> <= 768), two beyond (<8, 2>): with one row per lane n = 576 took 9 waves, three on
 // a SIMD, and a step cost what the three issue one after the other plus nine single-lane row publishes instead of three.
@@ -383,14 +484,21 @@ __device__ __forceinline__ void gj_panel_load(const double* __restrict__ A, cons
 // The elimination steps, then the pivot block into sh.LU (row-major in pivot order, identity beyond nbw) and the singular flag into
 // sh.s_sing: both are complete after the caller's next barrier.  mypos[q]: the pivot position row q of this thread took in this panel, or -1;
 // myperm (wave 0, lane j): the row that became pivot j.
-template <int NW, int RPL>
-__device__ __forceinline__ void gj_panel_factor(GjPanelShared<NW, RPL>& sh, double (&a)[RPL][GJ_NB], unsigned& live, int (&mypos)[RPL], int& myperm, int t, int nbw, int k0
+//
+// CMP (the <4, 1> instance) with cs != nullptr and nl = n - k0 <= GJ_CMAX live rows: the compacted chain above.  rank: this thread's row among
+// the live ones (gj_compact_rank).  mypos / myperm come out as from the four-wave chain: a thread learns the position its ORIGINAL row took
+// through cs.pos, so the callers' rowpos code is one for both chains.  The live count is n - k0 by construction (every earlier panel retired
+// 32 rows), so the choice is workgroup-uniform.  A wave without a live row does nothing at all.
+template <int NW, int RPL, bool CMP>
+__device__ __forceinline__ void gj_panel_factor(GjPanelShared<NW, RPL>& sh, double (&a)[RPL][GJ_NB], unsigned& live, int (&mypos)[RPL], int& myperm, int t, int nbw, int k0,
+                                                GjCompactShared* cs, int nl, int rank
 #ifdef DQ_GJ_STAMPS
                                                 , unsigned long long& gstart, unsigned long long& gsteps_end
 #endif
                                                 ) {
     constexpr int NWK = (NW + 1) & ~1;
     static_assert(RPL <= 4, "two key bits name the slot");
+    static_assert(!CMP || (NW == 4 && RPL == 1), "the compacted chain is written for one row per lane in at most four waves");
     const int lane = t & 63, wave = t >> 6;
     bool singular = false;
     myperm = 0;
@@ -399,6 +507,36 @@ __device__ __forceinline__ void gj_panel_factor(GjPanelShared<NW, RPL>& sh, doub
     for (int e = t; e < GJ_NB * GJ_NB; e += blockDim.x) (&sh.LU[0][0])[e] = ((e >> 5) == (e & 31)) ? 1.0 : 0.0;   // identity padding for nbw < 32
     if (t == 0) sh.s_sing = 0;
     if (t < 2 * NWK) (&sh.slot_key[0][0])[t] = 0ULL;      // waves that do not exist never publish: their keys stay "no candidate"
+    if constexpr (CMP) {
+        if (cs != nullptr && nl <= GJ_CMAX) {             // workgroup-uniform
+            cs->pos[t] = -1;
+            if ((live & 1u) && rank < GJ_CMAX) {          // (rank < nl always: the bound keeps a corrupt rowpos inside the buffer)
+#pragma unroll
+                for (int c = 0; c < GJ_NB; ++c) cs->rows[c][rank] = a[0][c];
+                cs->orow[rank] = t;
+            }
+            lds_wait();
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+#ifdef DQ_GJ_STAMPS
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gstart) :: "memory");
+#endif
+            if (wave == 0) {
+                if (nl <= 64) gj_chain_cw<1>(*cs, sh.LU, sh.s_sing, myperm, nl, lane, nbw, k0);
+                else gj_chain_cw<2>(*cs, sh.LU, sh.s_sing, myperm, nl, lane, nbw, k0);
+            }
+#ifdef DQ_GJ_STAMPS
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gsteps_end) :: "memory");
+            if (t == 0 && k0 == DQ_GJ_STAMP_K0 && blockIdx.x == 0 && blockIdx.y == 0)
+                printf("gj panel k0=%d grid.x=%d, compacted: %d live rows on one wave, clocks over %d steps incl. the read-back and the deposit: %llu\n", k0, (int)gridDim.x, nl, nbw, gsteps_end - gstart);
+#endif
+            lds_wait();
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            mypos[0] = cs->pos[t];
+            return;
+        }
+    }
     lds_wait();
     __builtin_amdgcn_s_barrier();                        // LDS only: loads the caller has in flight stay in flight
     asm volatile("" ::: "memory");
@@ -407,12 +545,12 @@ __device__ __forceinline__ void gj_panel_factor(GjPanelShared<NW, RPL>& sh, doub
     unsigned long long gst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gprev;
     asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gprev) :: "memory"); gstart = gprev;
 #endif
-    GjStepsMW<0, NW, RPL>::run(a, live, mypos, myperm, singular, lane, wave, nbw, k0, sh.slot_row, sh.slot_key GST_PASS);
+    GjStepsMW<0, NW, RPL, CMP>::run(a, live, mypos, myperm, singular, lane, wave, nbw, k0, sh.slot_row, sh.slot_key GST_PASS);
 #ifdef DQ_GJ_STAMPS
     gsteps_end = gprev;
-    if (t == 0 && k0 == 0 && blockIdx.x == 0 && blockIdx.y == 0)
-        printf("gj panel k0=0 grid.x=%d, %d waves x %d rows per lane, clocks over %d steps (each segment includes one stamp, ~130): (loop) %llu | search %llu | publish %llu | barrier %llu | keys %llu | row %llu | fma %llu | total %llu\n",
-               (int)gridDim.x, (int)(blockDim.x >> 6), RPL, nbw, gst[0], gst[1], gst[2], gst[3], gst[4], gst[5], gst[6], gprev - gstart);
+    if (t == 0 && k0 == DQ_GJ_STAMP_K0 && blockIdx.x == 0 && blockIdx.y == 0)
+        printf("gj panel k0=%d grid.x=%d, %d waves x %d rows per lane, clocks over %d steps (each segment includes one stamp, ~130): (loop) %llu | search %llu | publish %llu | barrier %llu | keys %llu | row %llu | fma %llu | total %llu\n",
+               k0, (int)gridDim.x, (int)(blockDim.x >> 6), RPL, nbw, gst[0], gst[1], gst[2], gst[3], gst[4], gst[5], gst[6], gprev - gstart);
 #endif
 
     lds_wait();
@@ -428,13 +566,34 @@ __device__ __forceinline__ void gj_panel_factor(GjPanelShared<NW, RPL>& sh, doub
     }
     if (singular && lane == 0) sh.s_sing = 1;
 }
+// the rank of this thread's row among the live rows of a panel that will be compacted (else 0) and their number nl: rowpos of this lane's row in EVERY wave, loaded in
+// the round of the panel's own loads, so that the wave offsets need no exchange.  pos: this thread's own entry, n <= 256.
+__device__ __forceinline__ int gj_compact_rank(const int* rowpos, int n, int t, bool compact, int& nl) {
+    int rank = 0;
+    nl = GJ_CMAX + 1;                                    // "not compacted"
+    if (compact) {                                       // workgroup-uniform
+        int tot = 0;
+        const int lane = t & 63, wave = t >> 6;
+        int pw[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const int r = lane + 64 * w; pw[w] = rowpos[r < n ? r : n - 1]; }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const unsigned long long b = __ballot(lane + 64 * w < n && pw[w] < 0);
+            rank += w < wave ? __popcll(b) : (w == wave ? __popcll(b & ((1ULL << lane) - 1ULL)) : 0);
+            tot += __popcll(b);
+        }
+        nl = tot < GJ_CMAX ? tot : GJ_CMAX;              // counted, = n - k0: wave 0 reads no slot that nobody wrote, whatever rowpos holds
+    }
+    return rank;
+}
 #ifdef DQ_GJ_STAMPS
 #define GJ_STAMP_VM(x) asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(x) :: "memory")
 #endif
 
 template <int NW, int RPL>
 __global__ __launch_bounds__(64 * NW) void gj_panel_mw_kernel(CMat Am, int* rowpos_p, long rowpos_stride, int* perm_p, long perm_stride, double* tinv_p,
-                                                          double* logabsdet, int accumulate, int* info, int n, int k0) {
+                                                          double* logabsdet, int accumulate, int* info, int n, int k0, int compact) {
     __shared__ __attribute__((aligned(16))) GjPanelShared<NW, RPL> sh;
     const int chain = blockIdx.y;
     const double* __restrict__ A = Am.at(chain);
@@ -451,10 +610,16 @@ __global__ __launch_bounds__(64 * NW) void gj_panel_mw_kernel(CMat Am, int* rowp
     int oldpos[RPL], mypos[RPL], myperm;
     double a[RPL][GJ_NB];
     gj_panel_load<NW, RPL, false>(A, rowpos, n, k0, nbw, t, a, live, oldpos);
+    constexpr bool CMP = NW == 4 && RPL == 1;              // late panels run on one wave (gj_panel_factor); the other instances name no buffer
+    __shared__ __attribute__((aligned(16))) std::conditional_t<CMP, GjCompactShared, int> s_cs;
+    GjCompactShared* cs = nullptr;
+    if constexpr (CMP) { if (compact) cs = &s_cs; }
+    int nl = GJ_CMAX + 1;
+    const int rank = CMP ? gj_compact_rank(rowpos, n, t, cs != nullptr && k0 > 0 && n - k0 <= GJ_CMAX, nl) : 0;      // (k0 = 0: rowpos holds the last solve's)
 #ifdef DQ_GJ_STAMPS
-    gj_panel_factor<NW, RPL>(sh, a, live, mypos, myperm, t, nbw, k0, gstart, gprev);
+    gj_panel_factor<NW, RPL, CMP>(sh, a, live, mypos, myperm, t, nbw, k0, cs, nl, rank, gstart, gprev);
 #else
-    gj_panel_factor<NW, RPL>(sh, a, live, mypos, myperm, t, nbw, k0);
+    gj_panel_factor<NW, RPL, CMP>(sh, a, live, mypos, myperm, t, nbw, k0, cs, nl, rank);
 #endif
 #pragma unroll
     for (int q = 0; q < RPL; ++q) {
@@ -473,7 +638,7 @@ __global__ __launch_bounds__(64 * NW) void gj_panel_mw_kernel(CMat Am, int* rowp
 #ifdef DQ_GJ_STAMPS
     unsigned long long gend;
     GJ_STAMP_VM(gend);
-    if (t == 0 && k0 == 0 && blockIdx.y == 0) printf("   prologue %llu | steps %llu | LU hand-over (+ printf) %llu | epilogue %llu\n", gstart - gentry, gprev - gstart, gmid - gprev, gend - gmid);
+    if (t == 0 && k0 == DQ_GJ_STAMP_K0 && blockIdx.y == 0) printf("   prologue %llu | steps %llu | LU hand-over (+ printf) %llu | epilogue %llu\n", gstart - gentry, gprev - gstart, gmid - gprev, gend - gmid);
 #endif
 }
 
@@ -615,7 +780,7 @@ __global__ __launch_bounds__(256) void gj_update_kernel(Mat Am, Mat Bm, Mat SAm,
 // counted wait in front of the first step covers the panel's loads only; they have clamped addresses and are masked at use.
 template <int NW, int RPL>
 __global__ __launch_bounds__(64 * NW) void gj_step_kernel(Mat Am, Mat Bm, Mat SAm, Mat Xm, const int* rowpos_old_p, int* rowpos_new_p, long rowpos_stride,
-                                                          double* logabsdet, int accumulate, int* info, int n, int k0, int nA, int nS, int nCA) {
+                                                          double* logabsdet, int accumulate, int* info, int n, int k0, int nA, int nS, int nCA, int compact) {
     static_assert(NW == 4, "the update's 2 x 2 waves are the panel's");
     __shared__ __attribute__((aligned(16))) GjPanelShared<NW, RPL> sh;
     __shared__ __attribute__((aligned(16))) double s_inv[4 * 256];      // the four 16 x 16 triangular inverses, column-major
@@ -640,6 +805,12 @@ __global__ __launch_bounds__(64 * NW) void gj_step_kernel(Mat Am, Mat Bm, Mat SA
     int oldpos[RPL], mypos[RPL], myperm;
     double a[RPL][GJ_NB];
     gj_panel_load<NW, RPL, true>(A, rowpos_old, n, k0, nbw, t, a, live, oldpos);
+    constexpr bool CMP = NW == 4 && RPL == 1;
+    __shared__ __attribute__((aligned(16))) std::conditional_t<CMP, GjCompactShared, int> s_cs;
+    GjCompactShared* cs = nullptr;
+    if constexpr (CMP) { if (compact) cs = &s_cs; }
+    int nl = GJ_CMAX + 1;
+    const int rank = CMP ? gj_compact_rank(rowpos_old, n, t, cs != nullptr && k0 > 0 && n - k0 <= GJ_CMAX, nl) : 0;      // (k0 = 0: rowpos holds the last solve's)
 
     const int row_tiles = nA + nS + 1;
     const int rt = blockIdx.x % row_tiles, ct = blockIdx.x / row_tiles;
@@ -674,9 +845,9 @@ __global__ __launch_bounds__(64 * NW) void gj_step_kernel(Mat Am, Mat Bm, Mat SA
     }
 
 #ifdef DQ_GJ_STAMPS
-    gj_panel_factor<NW, RPL>(sh, a, live, mypos, myperm, t, nbw, k0, gstart, gprev);
+    gj_panel_factor<NW, RPL, CMP>(sh, a, live, mypos, myperm, t, nbw, k0, cs, nl, rank, gstart, gprev);
 #else
-    gj_panel_factor<NW, RPL>(sh, a, live, mypos, myperm, t, nbw, k0);
+    gj_panel_factor<NW, RPL, CMP>(sh, a, live, mypos, myperm, t, nbw, k0, cs, nl, rank);
 #endif
 #pragma unroll
     for (int q = 0; q < RPL; ++q) {
@@ -770,7 +941,7 @@ __global__ __launch_bounds__(64 * NW) void gj_step_kernel(Mat Am, Mat Bm, Mat SA
 #ifdef DQ_GJ_STAMPS
     unsigned long long gend;
     GJ_STAMP_VM(gend);
-    if (t == 0 && k0 == 0 && blockIdx.x == 0 && blockIdx.y == 0)
+    if (t == 0 && k0 == DQ_GJ_STAMP_K0 && blockIdx.x == 0 && blockIdx.y == 0)
         printf("   fused step: prologue %llu | chain %llu | deposit (+ printf) %llu | inverses (wave 0) %llu | gather wait %llu | update %llu\n", gstart - gentry, gprev - gstart,
                gmid - gprev, ginv - gmid, ggather - ginv, gend - ggather);
 #endif
@@ -784,7 +955,7 @@ bool gj_fused_default(int n) { return n > 128 && n <= 256; }
 // perm / rowpos / rowpos_alt: n ints per chain.  logabsdet (optional) receives (+)= log|det A|; *info |= DQ_STATUS_PIVOT on a zero / NaN pivot.
 // fused: one gj_step_kernel per panel where an instance exists (gj_fused_fits); rowpos_alt is then the second half of rowpos.
 int launch_gj_solve(Mat A, Mat B, Mat X, Mat SA, double* tinv, int* perm, long perm_stride, int* rowpos, int* rowpos_alt, long rowpos_stride,
-                    double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, bool fused, hipStream_t s) {
+                    double* logabsdet, int accumulate_logdet, int* info, int n, int n_chains, bool fused, bool compact, hipStream_t s) {
     if (n > 1024) { set_error("gj_solve supports n <= 1024"); return -1; }
     if (fused && rowpos_alt && gj_fused_fits(n)) {
         int p = 0;
@@ -793,14 +964,14 @@ int launch_gj_solve(Mat A, Mat B, Mat X, Mat SA, double* tinv, int* perm, long p
             const int nA = (n + 31) / 32, nS = k0 / 32;
             const int nCA = (n - k0 - nbw + 31) / 32, nCB = (n + 31) / 32;
             hipLaunchKernelGGL((gj_step_kernel<4, 1>), dim3((nA + nS + 1) * (nCA + nCB), n_chains), dim3(256), 0, s, A, B, SA, X, (const int*)((p & 1) ? rowpos_alt : rowpos),
-                               (p & 1) ? rowpos : rowpos_alt, rowpos_stride, logabsdet, accumulate_logdet, info, n, k0, nA, nS, nCA);
+                               (p & 1) ? rowpos : rowpos_alt, rowpos_stride, logabsdet, accumulate_logdet, info, n, k0, nA, nS, nCA, compact ? 1 : 0);
         }
         DQ_HIP(hipGetLastError());
         return 0;
     }
     for (int k0 = 0; k0 < n; k0 += GJ_NB) {
         const dim3 pg(1, n_chains);
-#define DQ_GJ_PANEL(NW, RPL) hipLaunchKernelGGL((gj_panel_mw_kernel<NW, RPL>), pg, dim3(RPL == 1 ? 64 * ((n + 63) / 64) : 64 * NW), 0, s, CMat(A), rowpos, rowpos_stride, perm, perm_stride, tinv, logabsdet, accumulate_logdet, info, n, k0)
+#define DQ_GJ_PANEL(NW, RPL) hipLaunchKernelGGL((gj_panel_mw_kernel<NW, RPL>), pg, dim3(RPL == 1 ? 64 * ((n + 63) / 64) : 64 * NW), 0, s, CMat(A), rowpos, rowpos_stride, perm, perm_stride, tinv, logabsdet, accumulate_logdet, info, n, k0, compact ? 1 : 0)
         if (n > 768) DQ_GJ_PANEL(8, 2);
         else if (n > 576) DQ_GJ_PANEL(4, 3);
         else if (n > 512) DQ_GJ_PANEL(3, 3);

@@ -48,6 +48,17 @@ namespace {
 #define QST(i)
 #endif
 
+#ifdef DQ_QP_STAMPS
+#ifndef DQ_QP_STAMP_K
+#define DQ_QP_STAMP_K 0          // the panel whose ticks the stamp build prints (-DDQ_QP_STAMP_K=192: a compacted one at n = 256)
+#endif
+#define QP_QST_PARAM , unsigned long long* qst
+#define QP_QST_ARG , qst
+#else
+#define QP_QST_PARAM
+#define QP_QST_ARG
+#endif
+
 constexpr int QP_B = 16;         // panel width
 constexpr int QP_SR = 32;        // sketch rows formed by the update kernel (two MFMA row tiles)
 #ifndef QP_SEL_ROWS
@@ -216,6 +227,68 @@ __device__ __forceinline__ void select_step(double (&y)[CPL][QP_SEL], unsigned& 
     if (lane == 0 && wave == 0) sh.sel[J] = pcol;
 }
 
+// ---- selection on a compacted sketch: ONE wave, no workgroup barrier in the step ----
+// Late panels (<4, 1>, n - k <= QP_CMAX = 64 live columns): the live columns stand in rank order (= column order) in an LDS buffer, lane j
+// of wave 0 holds the j-th of them with its ORIGINAL column index mc, and wave 0 runs the 16 steps alone: the wave maximum of the keys is
+// the winner in every lane, the winner's lane puts its column into cand[] and the wave reads it back -- LDS accesses of one wave execute
+// in order, s_waitcnt lgkmcnt(0) is all the exchange needs.  The other waves wait at the barrier that closes the selection.
+// The bits are select_step's: norms, dots and updates are lane-local per column and written exactly as there; the key {norm^2 without
+// its low 11 bits | 1024 - column} carries the original column and is unique per live column, and a maximum of distinct keys does not
+// depend on which lane holds which column or on the order of the comparisons; the Householder scalars come from the same published
+// numbers (the winner's column and its lane-local tail).  Hence sel[], and with it L, d, R and jpvt, are bit for bit those of the
+// uncompacted selection.  (Two columns per lane for 64 < n - k <= 128 were measured and lost: DESIGN.md 5.7.)
+constexpr int QP_CMAX = 64;      // live columns up to which the selection is compacted
+template <int J, int NW>
+__device__ __forceinline__ void select_step_cw(double (&y)[QP_SEL], bool& live, int mc, int lane, PanelShared<NW>& sh) {
+    constexpr int par = J & 1;
+    double tl[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int i = J + 1; i < QP_SEL; ++i) tl[i & 3] = fma(y[i], y[i], tl[i & 3]);
+    const double tail = (tl[0] + tl[1]) + (tl[2] + tl[3]);
+    const double nrm2 = fma(y[J], y[J], tail);
+    const unsigned long long key = live ? (((unsigned long long)__double_as_longlong(nrm2) & ~0x7FFULL) | (unsigned long long)(1024 - mc)) : 0ULL;
+    const unsigned long long best = wave_max_u64(key);
+    if (best != 0ULL && key == best) {                               // one lane: keys of live columns are distinct
+#pragma unroll
+        for (int i = J & ~1; i < QP_SEL; i += 2) *reinterpret_cast<double2*>(&sh.cand[par][i]) = double2{y[i], y[i + 1]};
+        sh.cand[par][QP_SEL] = tail;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const int pcol = 1024 - (int)(best & 0x7FFULL);
+    const double* xs = sh.cand[par];
+    double x[QP_SEL];
+#pragma unroll
+    for (int i = J & ~1; i < QP_SEL; i += 2) { const double2 v = *reinterpret_cast<const double2*>(&xs[i]); x[i] = v.x; x[i + 1] = v.y; }
+    double beta, tau, scale;
+    householder<1>(x[J], xs[QP_SEL], beta, tau, scale);
+    const double st = -scale * tau;
+    double dt[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int i = J + 1; i < QP_SEL; ++i) dt[i & 3] = fma(x[i], y[i], dt[i & 3]);
+    const double dot = (dt[0] + dt[1]) + (dt[2] + dt[3]);
+    const double cf = st * fma(scale, dot, y[J]);
+#pragma unroll
+    for (int i = J + 1; i < QP_SEL; ++i) y[i] = fma(x[i], cf, y[i]);
+    if (mc == pcol) live = false;
+    if (lane == 0) sh.sel[J] = pcol;
+    asm volatile("" ::: "memory");                                   // the reads of cand[par] stay in front of the stores of step J + 2
+}
+// wave 0 after the compaction: lane j < nl takes the j-th live column out of cy[i][j] / ci[j] (into the registers of the column it
+// loaded), then the 16 steps
+template <int NW>
+__device__ __forceinline__ void select_compacted(double (&y)[QP_SEL], const double* cy, const int* ci, int nl, int lane, PanelShared<NW>& sh QP_QST_PARAM) {
+    bool live = lane < nl;
+    const int sc = live ? lane : 0;
+#pragma unroll
+    for (int i = 0; i < QP_SEL; ++i) { const double v = cy[i * QP_CMAX + sc]; y[i] = live ? v : 0.0; }
+    const int mc = live ? ci[sc] : -1;
+    QST(1)
+#define QP_CSTEP(J) select_step_cw<J, NW>(y, live, mc, lane, sh); QST(2 + J)
+    QP_CSTEP(0) QP_CSTEP(1) QP_CSTEP(2) QP_CSTEP(3) QP_CSTEP(4) QP_CSTEP(5) QP_CSTEP(6) QP_CSTEP(7)
+    QP_CSTEP(8) QP_CSTEP(9) QP_CSTEP(10) QP_CSTEP(11) QP_CSTEP(12) QP_CSTEP(13) QP_CSTEP(14) QP_CSTEP(15)
+#undef QP_CSTEP
+}
+
 // ---- panel: Householder step J on the 16 selected columns ----
 // a[b][16]: rows 64 NW b + 64 wave + 16 g + idx of column sel[c] (b < CPL: a lane owns one 16-row block in each "layer" of 64 NW rows);
 // diag bit b: that block is the panel's own rows k .. k + 15; rows above the panel (r < k) hold zeros.  x = column J below row k + J:
@@ -294,13 +367,6 @@ __host__ __device__ __forceinline__ long qp_off_vp(int n) { return qp_off_ticket
 __host__ __device__ __forceinline__ long qp_off_tm(int n) { return qp_off_vp(n) + (long)n * n; }
 __host__ __device__ __forceinline__ long qp_off_vtp(int n) { return qp_off_tm(n) + (long)QP_B * n; }
 
-#ifdef DQ_QP_STAMPS
-#define QP_QST_PARAM , unsigned long long* qst
-#define QP_QST_ARG , qst
-#else
-#define QP_QST_PARAM
-#define QP_QST_ARG
-#endif
 
 // The selection and the factorisation of the panel that starts at step k, by one workgroup of NW waves (64 NW CPL >= n: a lane owns CPL
 // columns in the selection and CPL 16-row blocks of one column in the panel).  Reads Y, pivpos and rows >= k of the selected columns of A;
@@ -309,16 +375,29 @@ __host__ __device__ __forceinline__ long qp_off_vtp(int n) { return qp_off_tm(n)
 // times myscale), wave 0 holds row c of T in trow.  Every global load has landed when step 0 of the panel passes its barrier;
 // pre() runs once the first round of loads (sketch, pivpos) is issued and before anything is waited for -- true: the workgroup leaves, the
 // function returns false --, mid() right after step 0 of the panel.  qp_panel_kernel and qp_step_kernel both call this body, so they factor bit for bit alike.
-template <int NW, int CPL, class Pre, class Mid>
+//
+// CMP (the <4, 1> instances: 128 < n <= 256) with cy != nullptr: a panel with n - k <= QP_CMAX live columns compacts them into cy / ci (LDS:
+// QP_SEL x QP_CMAX doubles, QP_CMAX ints, dead before and after the selection) and wave 0 alone selects (select_step_cw: the same bits).
+// The live count is n - k by construction -- every earlier panel retired 16 columns --, so the mode is workgroup-uniform and nothing is counted.
+template <int NW, int CPL, bool CMP, class Pre, class Mid>
 __device__ __forceinline__ bool qp_factor_panel(const double* A, const double* __restrict__ Y, const int* pivpos, int n, int k, PanelShared<NW>& sh,
                                                 double* tau_out, double (&a)[CPL][16], double (&trow)[QP_B], double& myscale, unsigned& diag, int& mycol,
-                                                Pre&& pre, Mid&& mid QP_QST_PARAM) {
+                                                double* cy, int* ci, Pre&& pre, Mid&& mid QP_QST_PARAM) {
+    static_assert(!CMP || (NW == 4 && CPL == 1), "the compacted selection is written for one column per lane in four waves");
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const bool compact = CMP && cy != nullptr && n - k <= QP_CMAX;      // workgroup-uniform
     QST(0)
     // ---- selection ----
     {
         unsigned live = 0u;
         double y[CPL][QP_SEL]; int pp[CPL];
+        int ppw[CMP ? 4 : 1];                                        // CMP: pivpos of this lane's column in EVERY wave, same round of loads: the wave offsets of the ranks need no exchange
+        if (CMP) {
+            if (compact) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) { const int col = lane + 64 * w; ppw[w] = pivpos[col < n ? col : n - 1]; }
+            }
+        }
 #pragma unroll
         for (int q = 0; q < CPL; ++q) {                              // one round of loads: clamped addresses, masked afterwards
             const int col = t + 64 * NW * q, cc = col < n ? col : n - 1;
@@ -337,11 +416,36 @@ __device__ __forceinline__ bool qp_factor_panel(const double* A, const double* _
             }
         }
         if (y[0][0] == 1.2345e300) live = 0u;                            // (stamps: forces the loads to have landed before the first stamp)
-        QST(1)
+        bool selected = false;
+        if constexpr (CMP) {
+            if (compact) {
+                QST(39)
+                // rank of a live column among the live ones, in column order: live lanes below it in its wave + the live counts of the waves below
+                int rank = 0, tot = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long b = __ballot(lane + 64 * w < n && ppw[w] < 0);
+                    rank += w < wave ? __popcll(b) : (w == wave ? __popcll(b & ((1ULL << lane) - 1ULL)) : 0);
+                    tot += __popcll(b);
+                }
+                const int nl = tot < QP_CMAX ? tot : QP_CMAX;        // counted, = n - k: wave 0 reads no slot that nobody wrote, whatever pivpos holds
+                if ((live & 1u) && rank < QP_CMAX) {                 // (rank < n - k <= QP_CMAX always: the bound keeps a corrupt pivpos inside the buffer)
+#pragma unroll
+                    for (int i = 0; i < QP_SEL; ++i) cy[i * QP_CMAX + rank] = y[0][i];
+                    ci[rank] = t;
+                }
+                lds_barrier();
+                if (wave == 0) select_compacted<NW>(y[0], cy, ci, nl, lane, sh QP_QST_ARG);
+                selected = true;
+            }
+        }
+        if (!selected) {
+            QST(1)
 #define QP_SEL_STEP(J) select_step<J, NW, CPL>(y, live, t, lane, wave, sh); QST(2 + J)
-        QP_SEL_STEP(0) QP_SEL_STEP(1) QP_SEL_STEP(2) QP_SEL_STEP(3) QP_SEL_STEP(4) QP_SEL_STEP(5) QP_SEL_STEP(6) QP_SEL_STEP(7)
-        QP_SEL_STEP(8) QP_SEL_STEP(9) QP_SEL_STEP(10) QP_SEL_STEP(11) QP_SEL_STEP(12) QP_SEL_STEP(13) QP_SEL_STEP(14) QP_SEL_STEP(15)
+            QP_SEL_STEP(0) QP_SEL_STEP(1) QP_SEL_STEP(2) QP_SEL_STEP(3) QP_SEL_STEP(4) QP_SEL_STEP(5) QP_SEL_STEP(6) QP_SEL_STEP(7)
+            QP_SEL_STEP(8) QP_SEL_STEP(9) QP_SEL_STEP(10) QP_SEL_STEP(11) QP_SEL_STEP(12) QP_SEL_STEP(13) QP_SEL_STEP(14) QP_SEL_STEP(15)
 #undef QP_SEL_STEP
+        }
     }
     lds_barrier();
     // ---- panel ----
@@ -398,7 +502,12 @@ __global__ __launch_bounds__(64 * NW) void qp_panel_kernel(Mat Am, QrWork w, int
 #endif
     double a[CPL][16], trow[QP_B], myscale;
     unsigned diag; int mycol;
-    qp_factor_panel<NW, CPL>(A, Y, pivpos, n, k, sh, tau + k, a, trow, myscale, diag, mycol, [] { return false; }, [] {} QP_QST_ARG);
+    constexpr bool CMP = NW == 4 && CPL == 1;                  // late panels select on a compacted sketch (qp_factor_panel); the other instances name no buffer
+    __shared__ double s_cy[CMP ? QP_SEL * QP_CMAX : 1];
+    __shared__ int s_ci[CMP ? QP_CMAX : 1];
+    double* cy = nullptr; int* ci = nullptr;
+    if constexpr (CMP) { if (w.pw_compact) { cy = s_cy; ci = s_ci; } }
+    qp_factor_panel<NW, CPL, CMP>(A, Y, pivpos, n, k, sh, tau + k, a, trow, myscale, diag, mycol, cy, ci, [] { return false; }, [] {} QP_QST_ARG);
     // ---- write-out: R0 / beta / reflectors in place, the clean reflector panel (unit diagonal, zeros above), T, jpvt, pivpos ----
 #pragma unroll
     for (int b = 0; b < CPL; ++b) {
@@ -429,8 +538,9 @@ __global__ __launch_bounds__(64 * NW) void qp_panel_kernel(Mat Am, QrWork w, int
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     QST(35)
     __syncthreads();
-    if (t == 0 && k == 0 && blockIdx.y == 0) {
-        printf("panel k=0 n=%d (100 MHz ticks x 24 = clk @2.4GHz): load Y %llu | sel steps", n, qst[1] - qst[0]);
+    if (t == 0 && k == DQ_QP_STAMP_K && blockIdx.y == 0) {
+        if (cy != nullptr && n - k <= QP_CMAX) printf("panel k=%d n=%d: compaction (ranks, LDS pass, barrier, wave 0's read-back) %llu of the load segment\n", k, n, qst[1] - qst[39]);
+        printf("panel k=%d n=%d (100 MHz ticks x 24 = clk @2.4GHz): load Y %llu | sel steps", k, n, qst[1] - qst[0]);
         for (int j = 0; j < 16; ++j) printf(" %llu", qst[2 + j] - qst[1 + j]);
         printf(" | gather %llu | panel steps", qst[18] - qst[17]);
         for (int j = 0; j < 16; ++j) printf(" %llu", qst[19 + j] - qst[18 + j]);
@@ -711,7 +821,13 @@ __global__ __launch_bounds__(64 * NW) void qp_step_kernel(Mat Am, QrWork w, int 
     // ---- phase 1 ----
     double a[CPL][16], trow[QP_B], myscale;
     unsigned diag; int mycol;
-    const bool factored = qp_factor_panel<NW, CPL>(A, Yr, pivpos, n, k, sh, s_tau, a, trow, myscale, diag, mycol, [&] {
+    // late panels of the <4, 1> instance select on a compacted sketch: the buffer is the head of red[][][], which nothing uses before phase 2
+    constexpr bool CMP = NW == 4 && CPL == 1;
+    static_assert(!CMP || sizeof(red) >= sizeof(double) * QP_SEL * QP_CMAX, "the compaction buffer is the reduction buffer");
+    __shared__ int s_ci[CMP ? QP_CMAX : 1];
+    double* cy = nullptr; int* ci = nullptr;
+    if constexpr (CMP) { if (w.pw_compact) { cy = &red[0][0][0]; ci = s_ci; } }
+    const bool factored = qp_factor_panel<NW, CPL, CMP>(A, Yr, pivpos, n, k, sh, s_tau, a, trow, myscale, diag, mycol, cy, ci, [&] {
         // the sketch loads are in flight beside the tiles': the retired test costs no round of its own
         if (__ballot(pp < 0) != 0ULL) return false;            // every wave sees the same 16 columns: uniform
         if (t == 0) s_ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -871,7 +987,8 @@ __global__ __launch_bounds__(64 * NW) void qp_step_kernel(Mat Am, QrWork w, int 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     QST(38)
     __syncthreads();
-    if (t == 0 && (k == 0 || k == n / 2) && blockIdx.x == 0 && blockIdx.y == 0) {
+    if (t == 0 && (k == DQ_QP_STAMP_K || k == n / 2) && blockIdx.x == 0 && blockIdx.y == 0) {
+        if (cy != nullptr && n - k <= QP_CMAX) printf("step k=%d n=%d: compaction (ranks, LDS pass, barrier, wave 0's read-back) %llu of the load segment\n", k, n, qst[1] - qst[39]);
         printf("step k=%d n=%d (100 MHz ticks): loads %llu | sel steps", k, n, qst[1] - qst[0]);
         for (int j = 0; j < 16; ++j) printf(" %llu", qst[2 + j] - qst[1 + j]);
         printf(" | gather %llu | panel steps", qst[18] - qst[17]);

@@ -2,7 +2,7 @@
 (scripts/stamp_build/libdqmc_hip_gjst.so: hipcc -DDQ_GJ_STAMPS, s_memtime between the phases of every step, summed over the panel;
 diagnostic, the waits it inserts change the overlap -- never used for timing results).  With DQMC_GJ_FUSED unset or 1 the sizes the fused
 step covers (64 < n <= 256) print gj_step_kernel's split (prologue | chain | deposit | inverses | gather wait | update) for workgroup 0 of the
-first panel, with DQMC_GJ_FUSED=0 the panel kernel's.   usage: gj_stamps.py [n ...]"""
+panel the library was built for (STAMP_K=<k0> scripts/scan_stamps.sh, default the first), with DQMC_GJ_FUSED=0 the panel kernel's.   usage: gj_stamps.py [n ...]"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,6 +1,6 @@
 """Where a panel of the panel-pivoted QR spends its time: runs dqmc_to_ldr once on a graded n x n matrix with the stamp build of
 qr_panel.hip (scripts/stamp_build/libdqmc_hip_qpst.so: hipcc -DDQ_QP_STAMPS, s_memtime at every step; diagnostic, never used for
-timing results) -- the kernel prints the ticks of panel k = 0.   usage: qp_stamps.py [n]"""
+timing results) -- the kernel prints the ticks of the panel the library was built for (STAMP_K=<k> scripts/scan_stamps.sh, default k = 0).   usage: qp_stamps.py [n]"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
