@@ -9,7 +9,7 @@ OBJS := $(CSRC)/gemm.o $(CSRC)/elementwise.o $(CSRC)/checkerboard.o $(CSRC)/upda
 
 all: dqmc_amd/libdqmc_hip.so dqmc_amd/libdqmc_host.so dqmc_amd/dqmc_driver oracle
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/wave.h include/dqmc_hip.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/scan_layout.h $(CSRC)/wave.h include/dqmc_hip.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/qr_colown.o: $(CSRC)/qr_colown_regs.inc

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include "scan_layout.h"
 
 struct dqmc_engine;
 
@@ -222,7 +223,6 @@ struct UpdateDesc {
     // It must not read the expv / invexpv row of the slice the launch walks (the walk rewrites that row in place).
     SliceRider rider;
 };
-constexpr int UPDATE_KD = 32;    // delayed-update window (accepted flips per flush)
 
 // ---- hand-off words of the persistent slice kernels (update.hip: slice_kernel, update_sm.hip: slice_sm_kernel) ----------------
 // One block per chain.  Every word a workgroup polls carries the LAUNCH number next to the window number:

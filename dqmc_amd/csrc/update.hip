@@ -31,7 +31,7 @@ using d4 = __attribute__((ext_vector_type(4))) double;
 
 __constant__ int c_proposal[4][3] = {{1, 2, 3}, {0, 2, 3}, {0, 1, 3}, {0, 1, 2}};   // include/field.h:45-48
 
-// dynamic LDS layout: UW[kd][n] (double2 {U, W}), diag[n], dlt[n], rbv[n], ur[n], tables[32] | site[n] (int) | newf[n] (bytes)
+// dynamic LDS layout (scan_layout.h): UW[kd][uw_pitch(n)] (double2 {U, W}; rows padded to a pitch of 1 mod 16: conflict-free pivot reads), diag[n], dlt[n], rbv[n], ur[n], tables[32] | site[n] (int) | newf[n] (bytes)
 //
 // Everything about a proposal that does not depend on G is evaluated for the whole slice up
 // front (thread j prepares proposal position j: site, delta, ratio prefactor, new field value,
@@ -50,12 +50,6 @@ __device__ __forceinline__ void st_coh(double* p, double x) {
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// bytes of dynamic LDS: UW[kd][n] | diag, dlt, rbv, ur [n] | tables[32] | site[n] | newf[n] (padded) | (register variant) diag2[n]
-__host__ __device__ inline size_t scan_lds_bytes(int n, int kd, bool regs) {
-    const size_t base = (((size_t)16 * kd * n + (size_t)n * 32 + 256 + (size_t)n * 4 + (size_t)n) + 63) & ~(size_t)63;
-    return base + (regs ? (size_t)n * 8 + 4 * (UPDATE_KD + 4) : 0);       // diag2 | acc_site[KD] | 4 spare words (verdicts of the persistent kernel's wave 0)
-}
-
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() carries a workgroup-scope release fence, which on
 // gfx950 is s_waitcnt vmcnt(0): every barrier of the walk would wait for the panel stores just issued (~500-1000
 // clk to L2 / memory) and for the G prefetch of the NEXT groups, i.e. the prefetch could never run ahead (measured:
@@ -68,7 +62,8 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 struct ScanShared {
-    double2* UW; double* diag; double* dlt; double* rbv; double* ur; double* tl; int* site; signed char* newf;
+    double2* UW; int up;          // pending pairs {U_m[j], W_m[j]} at UW[m * up + j], up = uw_pitch(n)
+    double* diag; double* dlt; double* rbv; double* ur; double* tl; int* site; signed char* newf;
     double* diag2 = nullptr;      // walk v3 only: second diagonal buffer
     int* acc_site = nullptr;      // walk v3 only: proposal index of pending pair m (KD entries)
 };
@@ -126,14 +121,14 @@ __device__ __forceinline__ bool scan_group(const double (&pc)[SCAN_PF], const do
                 // reads in flight before the first use, four independent accumulator pairs.
                 // 32-bit element offsets: LDS addresses are 32-bit, and size_t products per read cost more VALU
                 // time than the reads themselves (measured: 2000 cycles per accepted flip before, see scripts/scan_stamps.py)
-                const double2* own_p = sh.UW + j;                     // {U_m[j], W_m[j]} at own_p[m * n]
+                const double2* own_p = sh.UW + j;                     // {U_m[j], W_m[j]} at own_p[m * up]
                 const double2* piv_p = sh.UW + i;                     // {U_m[i], W_m[i]} (broadcast read)
                 double u1 = 0.0, w1 = 0.0, u2 = 0.0, w2 = 0.0, u3 = 0.0, w3 = 0.0;
                 int m = 0;
                 for (; m + 8 <= k; m += 8) {
                     double2 o[8], pv[8];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { const int off = (m + e) * n; o[e] = own_p[off]; pv[e] = piv_p[off]; }
+                    for (int e = 0; e < 8; ++e) { const int off = (m + e) * sh.up; o[e] = own_p[off]; pv[e] = piv_p[off]; }
                     uj += o[0].x * pv[0].y; wj += pv[0].x * o[0].y; u1 += o[1].x * pv[1].y; w1 += pv[1].x * o[1].y;
                     u2 += o[2].x * pv[2].y; w2 += pv[2].x * o[2].y; u3 += o[3].x * pv[3].y; w3 += pv[3].x * o[3].y;
                     uj += o[4].x * pv[4].y; wj += pv[4].x * o[4].y; u1 += o[5].x * pv[5].y; w1 += pv[5].x * o[5].y;
@@ -144,7 +139,7 @@ __device__ __forceinline__ bool scan_group(const double (&pc)[SCAN_PF], const do
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const int mm = (m + e < k) ? m + e : m;      // clamp: in-range address, contribution masked below
-                        const int off = mm * n; o[e] = own_p[off]; pv[e] = piv_p[off];
+                        const int off = mm * sh.up; o[e] = own_p[off]; pv[e] = piv_p[off];
                     }
 #pragma unroll
                     for (int e = 1; e < 8; ++e) if (m + e >= k) { o[e].x = 0.0; o[e].y = 0.0; }
@@ -162,7 +157,7 @@ __device__ __forceinline__ bool scan_group(const double (&pc)[SCAN_PF], const do
             lds_barrier();                                      // every lane has read diag[i] and the pivot entries
             if (live) {
                 const double pu = pref * uj;
-                sh.UW[k * n + j] = make_double2(pu, wj);
+                sh.UW[k * sh.up + j] = make_double2(pu, wj);
                 sh.diag[j] += pu * wj;
                 if (COH) { st_coh(Up + k * n + j, pu); st_coh(Wp + k * n + j, wj); }
                 else { Up[k * n + j] = pu; Wp[k * n + j] = wj; }    // the flush kernel's operands, stored as we go (fire and forget)
@@ -244,7 +239,7 @@ __device__ __forceinline__ void walk6_load_group(const double* __restrict__ G, c
 constexpr unsigned SLICE_SPIN_LIMIT = 1u << 22;     // polls (>= 1 us each) a resident partner is given
 constexpr unsigned SLICE_CENSUS_SPINS = 256;        // polls the walk grants late flush workgroups before it goes solo (~100-200 us)
 
-__device__ __attribute__((noinline)) void solo_flush(double* G, double* GT, const double2* UW, int n, int k);
+__device__ __attribute__((noinline)) void solo_flush(double* G, double* GT, const double2* UW, int up, int n, int k);
 // ---- the walk workgroup's side of the persistent kernel's hand-off (protocol: see slice_kernel) ----
 // census: has every flush workgroup checked in?  `first` is wave 0's load of the check-in words issued ahead of the caller's drain.
 // Returns true when some are still missing after the bounded wait (the walk then goes solo).  Block-wide (two barriers).
@@ -312,6 +307,7 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
                                             const double* __restrict__ GT, const UpdateDesc& d, long slice_off, int chain, int8_t* fields_g,
                                             double* __restrict__ Up, double* __restrict__ Wp, AS& as PROF_ARG) {
     const int lane = threadIdx.x & 63, r16 = lane & 15, q8 = lane & 7;
+    const int row_a = r16 * sh.up, row_b = (16 + r16) * sh.up;                  // the lane's two rows of the pivot reads below, in elements of UW
     DQ_W6_RESERVE;
     int par = 0, k = 0;
 #ifdef DQ_SCAN_STAMPS
@@ -326,7 +322,7 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
             slice_wait_arrivals(as.sy, as.epoch, as.win, as.F, as.info);
             DQ_ST(STAMP(tf1))
             DQ_W6_REBASE;
-            if (live) for (int t = 0; t < k - DQ_W6_KPUB; ++t) sh.UW[t * n + j] = sh.UW[(DQ_W6_KPUB + t) * n + j];
+            if (live) for (int t = 0; t < k - DQ_W6_KPUB; ++t) sh.UW[t * sh.up + j] = sh.UW[(DQ_W6_KPUB + t) * sh.up + j];
             if (j < k - DQ_W6_KPUB) sh.acc_site[j] = sh.acc_site[DQ_W6_KPUB + j];
             k -= DQ_W6_KPUB; ++as.win; as.inflight = false;
             as.base = (as.base + DQ_W6_KPUB) & SLICE_BASE_MASK;            // the confirmed window's ring rows are behind the walk now
@@ -381,8 +377,12 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
             // pivot entries of the pending pairs, broadcast by DPP in the pass below: lane r16 of every row holds {U_m[i], W_m[i]} for
             // m = r16 (pa) and m = 16 + r16 (pb); entries m >= k are never used.  Read here, in front of the asm statements (their
             // "memory" clobbers pin LDS reads behind them): the LDS latency runs under the wait and the pick
-            const int kc = max(k - 1, 0);
-            const double2 pa = sh.UW[min(r16, kc) * n + i], pb = sh.UW[min(16 + r16, kc) * n + i];
+            // Rows of the padded pitch sh.up = 1 (mod 16): the 16 lanes the LDS serves together read 16 different bank quadruples, 4 cycles
+            // per read for every k and i (pitch n: 4 min(16, k) and 4 max(1, k - 16), scan_layout.h).  The clamp is applied to the row
+            // offsets (min(r, kc) * up = min(r * up, kc * up)): the pitch is no power of two, and a vector multiply per read would sit
+            // in front of the reads on every accepted flip
+            const int kc = max(k - 1, 0) * sh.up;
+            const double2 pa = sh.UW[min(row_a, kc) + i], pb = sh.UW[min(row_b, kc) + i];
             const double pref = dl_p / r_p;                                      // source/model.cpp:132 (IEEE division) for the accepted proposal only, issued behind the LDS reads: its dozen dependent operations run under their latency
             // the pivot's G column / row elements from set gs: this group's 16 loads are done once at most the 32 younger ones are pending
             int ulo, uhi, wlo, whi;
@@ -404,7 +404,7 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
                 if (j == i) wj -= 1.0;                                           // V(i) -= 1 (source/model.cpp:135)
                 const double pu = pref * uj;
                 dg += pu * wj;
-                if (live) { sh.UW[k * n + j] = make_double2(pu, wj); (par ? sh.diag : sh.diag2)[j] = dg; }     // slot k / the diagonal buffer no wave is reading
+                if (live) { sh.UW[k * sh.up + j] = make_double2(pu, wj); (par ? sh.diag : sh.diag2)[j] = dg; }     // slot k / the diagonal buffer no wave is reading
                 if (j == 0) sh.acc_site[k] = p;                                  // fields are written at window end
                 if constexpr (AS::stream) {
                     // the pair leaves for ring row (base + k) & 63 now.  Inline asm, as the prefetch loads are: the compiler's waitcnt
@@ -444,7 +444,7 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
                             __hip_atomic_store(&as.sy->seq, ((unsigned long long)slice_tag(as.epoch, as.win) << 32) | SLICE_SOLO_BIT | (unsigned)k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             __hip_atomic_fetch_add(&as.sy->solo_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         }
-                        solo_flush(const_cast<double*>(G), const_cast<double*>(GT), sh.UW, n, k);
+                        solo_flush(const_cast<double*>(G), const_cast<double*>(GT), sh.UW, sh.up, n, k);
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         __syncthreads();
                         as.published += k; k = 0; ++as.win;
@@ -494,8 +494,8 @@ __device__ __forceinline__ int walk_window6(const ScanShared& sh, int& pos, doub
 }
 
 __device__ __forceinline__ void scan_shared_init(ScanShared& sh, unsigned char* smem, int n, int kd, bool regs) {
-    sh.UW = reinterpret_cast<double2*>(smem);
-    sh.diag = reinterpret_cast<double*>(sh.UW + (size_t)kd * n);
+    sh.UW = reinterpret_cast<double2*>(smem); sh.up = uw_pitch(n);
+    sh.diag = reinterpret_cast<double*>(sh.UW + (size_t)kd * sh.up);
     sh.dlt = sh.diag + n; sh.rbv = sh.dlt + n; sh.ur = sh.rbv + n; sh.tl = sh.ur + n;
     sh.site = reinterpret_cast<int*>(sh.tl + 32);
     sh.newf = reinterpret_cast<signed char*>(sh.site + n);
@@ -669,7 +669,7 @@ __global__ __launch_bounds__(256) void flush_kernel(UpdateDesc d, int tiles_per_
 // clocks).  Plain loads and stores: only this workgroup touches the chain during the launch, and workgroup-scope synchronisation
 // (barrier) is all its waves need to see each other's stores through the CU's own L1.
 template <int NB>
-__device__ __forceinline__ void flush_tiles_lds(double* __restrict__ G, double* __restrict__ GT, const double2* __restrict__ UW, int st0, int st_step,
+__device__ __forceinline__ void flush_tiles_lds(double* __restrict__ G, double* __restrict__ GT, const double2* __restrict__ UW, int up, int st0, int st_step,
                                                 int n_st, int tiles16, int n, int k, int lane) {
     const int r = lane & 15, kk = lane >> 4;
     double gv[NB][4], gt[NB][4];
@@ -698,7 +698,7 @@ __device__ __forceinline__ void flush_tiles_lds(double* __restrict__ G, double* 
             const int m = 4 * s + kk;
             const bool ok = m < k;
             const int mc = min(m, k - 1);
-            const double um = (ok && a_ok) ? UW[mc * n + a].x : 0.0, wm = (ok && b_ok) ? UW[mc * n + b].y : 0.0;
+            const double um = (ok && a_ok) ? UW[mc * up + a].x : 0.0, wm = (ok && b_ok) ? UW[mc * up + b].y : 0.0;
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wm, um, acc, 0, 0, 0);                 // rows <-> b, cols <-> a
             acc_t = __builtin_amdgcn_mfma_f64_16x16x4f64(um, wm, acc_t, 0, 0, 0);             // rows <-> a, cols <-> b
         }
@@ -744,10 +744,10 @@ __device__ __forceinline__ void flush_tiles_lds(double* __restrict__ G, double* 
 // A called function is NOT bound by the kernel's register budget (its ISA uses v128 and up freely) and the compiler saves nothing of the
 // hand-managed file around the call: every call site sits where that file is dead -- all pending pairs have just been applied (k = 0
 // afterwards) and the prefetch sets are reloaded from the new G right after it.
-__device__ __attribute__((noinline)) void solo_flush(double* G, double* GT, const double2* UW, int n, int k) {
+__device__ __attribute__((noinline)) void solo_flush(double* G, double* GT, const double2* UW, int up, int n, int k) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tiles16 = (n + 15) / 16, n_st = tiles16 * tiles16;
-    for (int st = wave; st < n_st; st += 4 * 4) flush_tiles_lds<4>(G, GT, UW, st, 4, n_st, tiles16, n, k, lane);
+    for (int st = wave; st < n_st; st += 4 * 4) flush_tiles_lds<4>(G, GT, UW, up, st, 4, n_st, tiles16, n, k, lane);
 }
 
 // ---- the rider: a B-bar product in the flush workgroups' idle time ----
@@ -908,7 +908,7 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_kernel(UpdateDesc d, S
             if (solo) {
                 // nobody else touches G during this launch: apply the window from the LDS pair store (plain accesses, this CU's L1 is
                 // write-through; the walk's own sc1 loads are served by the L2 the stores went to)
-                if (k > 0) solo_flush(G, GT, sh.UW, n, k);
+                if (k > 0) solo_flush(G, GT, sh.UW, sh.up, n, k);
                 if (final) break;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
@@ -983,7 +983,7 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_solo_kernel(UpdateDesc
         __syncthreads();                                              // every pair of the window is in LDS
         if (k > 0) {
             const int n_st = tiles16 * tiles16;                       // 16x16 sub-tiles of G (and their mirrors in GT): wave w takes w, w + 4, ...
-            for (int st = wave; st < n_st; st += 4 * 8) flush_tiles_lds<8>(G, GT, sh.UW, st, 4, n_st, tiles16, n, k, lane);
+            for (int st = wave; st < n_st; st += 4 * 8) flush_tiles_lds<8>(G, GT, sh.UW, sh.up, st, 4, n_st, tiles16, n, k, lane);
         }
         if (pos >= n) break;
         __syncthreads();                                              // fence + barrier: the flushed tiles are visible to every wave of this workgroup
@@ -991,15 +991,6 @@ __global__ __launch_bounds__(256) DQ_WALK_REGS void slice_solo_kernel(UpdateDesc
         __syncthreads();
     }
     if (j == 0) { int* acc = d.acc_out + (long)chain * d.acc_stride + acc_slot; *acc = (resume ? *acc : 0) + total_acc; }
-}
-
-static int pick_kd(int n) {
-    // LDS budget: 16*kd*n + n*(5*8+4+1) + tables <= ~150 KiB
-    const long budget = 150 * 1024 - (long)n * 48 - 1024;
-    long kd = budget / (16L * n);
-    if (kd > UPDATE_KD) kd = UPDATE_KD;
-    if (kd < 1) kd = 1;
-    return (int)kd;
 }
 
 // ---- co-residency of the persistent slice kernel ------------------------------------------------------------------------
@@ -1036,13 +1027,13 @@ void slice_release(int device, int n, int n_chains) {
 
 // kernels with more than 64 KiB of dynamic LDS need the attribute on every device they run on (init_device_kernels, engine.hip)
 int update_init_device() {
-    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<0, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<256, UPDATE_KD, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<0, 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<256, UPDATE_KD, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_solo_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS_LIMIT));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS_LIMIT));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<0, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS_LIMIT));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<256, UPDATE_KD, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS_LIMIT));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<0, 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS_LIMIT));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<256, UPDATE_KD, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS_LIMIT));
+    DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(slice_solo_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN_LDS_LIMIT));
     return 0;
 }
 
@@ -1053,6 +1044,7 @@ int launch_update_slice(SlicePath path, const UpdateDesc& d, int l, int acc_slot
     const int threads = ((n + 63) / 64) * 64;
     const bool regs = threads <= 256;                               // walk v3 (register-resident pending pairs, needs GT)
     size_t lds = scan_lds_bytes(n, kd, regs);
+    if (lds > SCAN_LDS_LIMIT) { set_error("local update: the walk's LDS layout exceeds the CU's LDS"); return -1; }
     const int tiles = (n + 31) / 32;
     if (!regs && path != SlicePath::Pairs && path != SlicePath::PersistentSubmatrix) { set_error("local update: the walk kernels of update.hip need n_sites <= 256"); return -1; }
     if (regs || path == SlicePath::PersistentSubmatrix) {          // the walk reads rows of G from GT
